@@ -9,6 +9,18 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   barrier + torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE
   JSON line.
 
+A plain run does only what the headline needs: inputs, warm-up (the --settle-ms ramp, the event pass's steps
+without their events, then the W steps), the K timed steps, the outputs if --dump-outputs is given, and the
+line (metric, value, unit, ms_per_step, dtype, config).  Everything else it measures or checks -- the parity guard, the per-kernel event pass and the roofline
+figures taken from it, the fp16 and drop-in siblings, the CPU baseline, the N > 1 exchange step -- runs only
+with --full.
+
+--dump-outputs DIR  after the timed steps, the arrays the timed path returned in its LAST step (rank 0): out,
+  grad_value, grad_loc, grad_attn, as DIR/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS elements
+  is written as a fixed, seeded sample of its flattened elements (the same positions every run; at most 32 MiB
+  in all).  The inputs depend only on the arguments (seeded generators), so two builds can be compared output
+  for output.
+
 Workload (BASELINE.json configs[1] / north_star synthetic tensors, SURVEY.md 8d
 "Config 2"):  per GPU  B=8, Nq=4096, n_levels=4 (64^2,32^2,16^2,8^2 -> S=5440), n_heads=8,
 n_points=4, C=1024 (D=128), bf16 storage / fp32 arithmetic, synthetic inputs in the
@@ -21,12 +33,12 @@ Multi-GPU: the path shards on the batch axis with no data-path collective
 (SURVEY.md 8e); every rank processes its own B samples -> "scaling": "weak";
 value = N * B * K / t_max.
 
-The K timed steps run clean (one C call per pass, no events).  Per-kernel times come from a
+The K timed steps run clean (one C call per pass, no events).  Per-kernel times (--full) come from a
 SEPARATE pass of --event-steps steps before the warm-up (HIP events recorded on the launch stream
-around every C-ABI launch), so ms_per_step does not depend on the sampling.  Order of a run: inputs,
+around every C-ABI launch), so ms_per_step does not depend on the sampling.  Order of a --full run: inputs,
 parity guard, event pass, W warm-up steps, barrier + synchronise, K timed steps, barrier + synchronise.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   roofline     dominant kernel's algorithmic bytes per launch / its mean duration (the event
                pass) vs 8 TB/s; "traffic" = HBM bytes of that kernel from profiles/pmc_traffic.json
                when that file has an entry for this workload and kernel ("traffic_from" names the
@@ -211,6 +223,23 @@ def timed_steps(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+DUMP_MAX_ELEMS = 1 << 21       # per array: 8 MiB of float32; four arrays -> at most 32 MiB
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """Writes every array as ``outdir/<name>.npy`` in float32: whole if it has at most DUMP_MAX_ELEMS elements,
+    else the elements at DUMP_MAX_ELEMS sorted positions of its flattened form drawn by a CPU generator seeded
+    with ``seed`` (the same positions on every run and build)."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
+
+
 def fp16_sibling(w, device, shapes, start, steps=20, warmup=10):
     """The headline shape in fp16 -- the only 16-bit type the reference's op has (ms_deform_attn_cuda.cu:65 dispatches
     fp64 / fp32 / fp16; training is fp16, configs/release/mm_pretrain.yaml:3) and so the only one in which BASELINE's
@@ -386,8 +415,15 @@ def main():
                          "error against the oracle slab, and the reference's call pattern (fresh level tensors per call)")
     ap.add_argument("--exchange-in-step", action="store_true",
                     help="N > 1: the feature all-gather of BASELINE config 5 is issued on a side stream inside every "
-                         "timed step, overlapping the op (SURVEY 8e); default: timed after the main region")
+                         "timed step, overlapping the op (SURVEY 8e); default: timed after the main region (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: parity guard, per-kernel event pass and roofline figures, "
+                         "fp16 and drop-in siblings, CPU baseline, the N > 1 exchange step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (out and the three gradients) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -444,7 +480,7 @@ def main():
         res = torch.autograd.grad(out, (value, loc, attn), grad)
         if overlap is not None:
             overlap.join()
-        return res
+        return (out,) + tuple(res)
 
     def fence():
         torch.cuda.synchronize()
@@ -456,17 +492,19 @@ def main():
     # properties of the op on this very workload (tests/test_op_gpu.py::test_full_size_properties): out is
     # linear in value and in attn, so <value, dL/dvalue> = <attn, dL/dattn> = <out, grad> (Euler); finite outputs.
     # (MMFS_EXPERIMENT=1: kernel-timing experiments with deliberately wrong arithmetic; the line is tagged)
+    # (--full only: a plain run checks nothing; --dump-outputs lets two builds be compared instead)
     experiment = os.environ.get("MMFS_EXPERIMENT") == "1"
-    out = MSDeformAttnFunction.apply(value, shapes, start, loc, attn, 1)
-    gv, gl, ga = torch.autograd.grad(out, (value, loc, attn), grad)
-    og = (out.double() * grad.reshape(out.shape).double()).sum()
-    rel = {"f32": 1e-4, "f16": 4e-3, "bf16": 3e-2}[w["dtype"]]
-    e1 = abs(float((gv.double() * value.double()).sum() - og)); e2 = abs(float((ga.double() * attn.double()).sum() - og))
-    assert experiment or bool(torch.isfinite(out).all() and torch.isfinite(gv).all() and torch.isfinite(gl).all() and torch.isfinite(ga).all()), "non-finite output"
-    assert experiment or e1 <= rel * abs(float(og)) + rel and e2 <= rel * abs(float(og)) + rel, f"parity guard failed: {e1:.3e} {e2:.3e} vs {float(og):.3e}"
-    del out, gv, gl, ga
+    if args.full:
+        out = MSDeformAttnFunction.apply(value, shapes, start, loc, attn, 1)
+        gv, gl, ga = torch.autograd.grad(out, (value, loc, attn), grad)
+        og = (out.double() * grad.reshape(out.shape).double()).sum()
+        rel = {"f32": 1e-4, "f16": 4e-3, "bf16": 3e-2}[w["dtype"]]
+        e1 = abs(float((gv.double() * value.double()).sum() - og)); e2 = abs(float((ga.double() * attn.double()).sum() - og))
+        assert experiment or bool(torch.isfinite(out).all() and torch.isfinite(gv).all() and torch.isfinite(gl).all() and torch.isfinite(ga).all()), "non-finite output"
+        assert experiment or e1 <= rel * abs(float(og)) + rel and e2 <= rel * abs(float(og)) + rel, f"parity guard failed: {e1:.3e} {e2:.3e} vs {float(og):.3e}"
+        del out, gv, gl, ga
 
-    # ---- per-kernel HIP events, recorded on the launch stream around every C-ABI launch: a pass of its
+    # ---- per-kernel HIP events (--full), recorded on the launch stream around every C-ABI launch: a pass of its
     # own, BEFORE the warm-up (bracketing every launch costs ~45 us of host work per step, and the stage-by-
     # stage calls are not what production issues: neither belongs in the timed region)
     t_settle = time.perf_counter()
@@ -478,20 +516,24 @@ def main():
     if not args.no_kernel_events:
         for _ in range(max(args.warmup, 40)):      # (its own warm-up: the averages are of a warm GPU, like the rocprofv3 trace's)
             step()
-        MSDA._event_log = log
-        for i in range(max(1, args.event_steps)):
+        MSDA._event_log = log if args.full else None     # (a plain run takes the same steps unbracketed: its timed
+        for i in range(max(1, args.event_steps)):       # steps start from the state a --full run's do)
             step()
         fence()
         MSDA._event_log = None
     for _ in range(args.warmup):
         step()
     fence()
-    # ---- the timed region: K clean steps (every pass ONE C call, like production)
+    # ---- the timed region: K clean steps (every pass ONE C call, like production); the last one's results are kept
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step()
+    last = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("out", "grad_value", "grad_loc", "grad_attn"), last)))
+    del last
     if args.no_kernel_events:
         if rank == 0:
             print(json.dumps({"ms_per_step": round(elapsed / args.steps * 1e3, 4), "note": "no kernel events"}))
@@ -503,6 +545,23 @@ def main():
     elapsed = float(t.item())
 
     if rank == 0:
+        Leff = len(w["shapes"]) * w["n"]
+        res = {
+            "metric": "mmfs_ms_deform_attn_fwd_bwd_samples_per_sec",
+            "value": round(world * w["B"] * args.steps / elapsed, 2),
+            "unit": "samples/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": w["dtype"], "data": "synthetic" if not experiment else "synthetic; EXPERIMENT BUILD, PARITY GUARD OFF -- not a result",
+            "config": {"workload": f"{args.workload}{'' if args.loc_dist == 'uniform' else '@' + args.loc_dist}{'' if args.visible == 'all' else '@' + args.visible}: ms_deform_attn fwd+bwd, per-GPU B={w['B']} Nq={w['Nq']} "
+                                   f"L={Leff} H={w['H']} P={w['P']} C={w['H'] * w['D']} S={sum(h * x for h, x in w['shapes']) * w['n']}",
+                       "global_batch": world * w["B"], "parallelism": f"batch-sharded x{world}, no collective"},
+            "levels": "fresh per call, unregistered (reference call pattern)" if args.fresh_levels else
+                      "fresh tensors built per call but NOT used (registered pair to the op)" if args.fresh_levels_unused else
+                      "make_level_tables (built once, known to the shim)",
+        }
+    if rank == 0 and args.full:
         e = torch.empty((), dtype=DTYPES[w["dtype"]]).element_size()
         per_kernel = {}
         for name, a, b in log:
@@ -525,18 +584,7 @@ def main():
                 traffic_from = prov if traffic is not None else None
             except Exception:
                 traffic = None
-        Leff = len(w["shapes"]) * w["n"]
-        res = {
-            "metric": "mmfs_ms_deform_attn_fwd_bwd_samples_per_sec",
-            "value": round(world * w["B"] * args.steps / elapsed, 2),
-            "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": w["dtype"], "data": "synthetic" if not experiment else "synthetic; EXPERIMENT BUILD, PARITY GUARD OFF -- not a result",
-            "config": {"workload": f"{args.workload}{'' if args.loc_dist == 'uniform' else '@' + args.loc_dist}{'' if args.visible == 'all' else '@' + args.visible}: ms_deform_attn fwd+bwd, per-GPU B={w['B']} Nq={w['Nq']} "
-                                   f"L={Leff} H={w['H']} P={w['P']} C={w['H'] * w['D']} S={sum(h * x for h, x in w['shapes']) * w['n']}",
-                       "global_batch": world * w["B"], "parallelism": f"batch-sharded x{world}, no collective"},
+        res.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "traffic_from": traffic_from,
@@ -548,13 +596,10 @@ def main():
                              if k in ab and v > 0 and ab[k] > 0},
             # event brackets cost a few us each and span a stage's helper launches: their sum may exceed the clean step
             "event_overhead_us": round(sum(mean_ms.values()) * 1e3 - elapsed / args.steps * 1e6, 2),
-            "levels": "fresh per call, unregistered (reference call pattern)" if args.fresh_levels else
-                      "fresh tensors built per call but NOT used (registered pair to the op)" if args.fresh_levels_unused else
-                      "make_level_tables (built once, known to the shim)",
             # whole step against the roofline: algorithmic bytes of forward + backward / the clean step time
             "fwdbwd_hbm_frac": round(ab["fwdbwd"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
             "kernels_hbm_frac": round(ab["fwdbwd"] / (sum(mean_ms.values()) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-        }
+        })
         # the WHOLE step against the roofline (SURVEY 8d's fwdbwd_bytes / the clean step time), against the 8 TB/s of the
         # data sheet and against the 6.29 TB/s a plain copy reaches on this part (MI355X_MICROARCH.md); forward and
         # backward separately from the per-kernel events
@@ -591,7 +636,7 @@ def main():
             except Exception as e:      # noqa: BLE001  (the checker is test infrastructure: its absence is reported, not fatal)
                 res["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
     ex = None
-    if dist is not None:
+    if dist is not None and args.full:
         # every rank says whether it can enter the collectives BEFORE any of them does: a rank that fails
         # inside its own set-up must not leave the others waiting in an all-gather
         ok = torch.ones((), dtype=torch.int32, device=device)

@@ -1,8 +1,13 @@
 """bench.py's multi-GPU launch logic, on the CPU: `--gpus N` must never degrade silently to one rank
 (`--gpus 8` without WORLD_SIZE ran ONE rank and printed n_gpus: 1)."""
+import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -56,3 +61,43 @@ def test_eight_ranks_compose_and_refuse_on_fewer_devices():
                        capture_output=True, text=True, env=_env(), timeout=300)
     assert r.returncode == 2
     assert "refusing to run fewer ranks" in r.stderr and "n_gpus" not in r.stdout
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays_at_fixed_positions(tmp_path):
+    """--dump-outputs: small arrays whole, larger ones as the same seeded sample of positions on every call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4).to(torch.bfloat16)
+    big = torch.randn(bench.DUMP_MAX_ELEMS + 1000, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.array_equal(s, small.float().numpy())
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert np.isin(a, big.float().numpy()).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run: the headline line with exactly --steps timed steps and none of --full's figures; --dump-outputs
+    writes the last step's out and gradients (grad_value, the one array above the size cap, as a sample)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--nq", "256",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res
+    assert res["steps"] == 3 and res["dtype"] == "bf16" and res["ms_per_step"] > 0
+    assert not {"roofline", "kernels_mean_us", "fp16", "dropin_unchanged_ms", "cpu_baseline", "exchange"} & set(res)
+    want = {"out": (8, 256, 1024), "grad_value": (bench.DUMP_MAX_ELEMS,), "grad_loc": (8, 256, 8, 4, 4, 2),
+            "grad_attn": (8, 256, 8, 4, 4)}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(n + ".npy" for n in want)
+    for name, shape in want.items():
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+    assert 0.0 <= np.load(tmp_path / "out.npy").min() and np.load(tmp_path / "out.npy").max() <= 1.01
