@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 13  /* 13: + mmfs_msda_backward_sorted (+ _workspace_bytes): the whole backward on the cell-sorted records -- grad_loc / grad_attn
+#define MMFS_MSDA_ABI_VERSION 14  /* 14: + mmfs_msda_forward_shared, mmfs_sample_forward_heads_shared: one value bank of Bv rows serves
+                                   *     B = g * Bv query rows (MMFS_BANK_TILE / MMFS_BANK_INTERLEAVE) without being copied
+                                   * 13: + mmfs_msda_backward_sorted (+ _workspace_bytes): the whole backward on the cell-sorted records -- grad_loc / grad_attn
                                    *     from the records the grad_value sort makes (csrc/msda_bwd_taps_sorted.hip), no per-sample value-row gather;
                                    *     GONE: the workgroup-local grad_value of the small levels (csrc/msda_gv_mma.hip: parity-green, slower on every
                                    *     shipped geometry for three rounds) with stage MMFS_HYB_BWD_VALUE_BLOCKS, MMFS_BWD_VALUE_SORTED_ONLY /
@@ -143,6 +145,27 @@ int mmfs_msda_forward_flags(int dtype,
                             const void *loc, const void *attn, void *out,
                             int64_t B, int64_t S, int64_t H, int64_t D,
                             int64_t L, int64_t Nq, int64_t P, unsigned flags, void *stream);
+
+/*
+ * Shared bank.  Classifier-free guidance doubles the feature bank (torch.cat([bank] * 2)) and beam search repeats it per beam
+ * (bank.repeat_interleave(num_beams, 0)): g query rows then read identical banks.  Here ``value`` holds the bank ONCE,
+ * [Bv, S, H, D], and serves the B = g * Bv query rows of loc / attn / out (Bv > 0, B % Bv == 0):
+ *     query row b reads bank row  vrow(b) = (b / div) % Bv
+ *   MMFS_BANK_TILE        div = 1   the order of torch.cat([bank] * g)        (classifier-free guidance)
+ *   MMFS_BANK_INTERLEAVE  div = g   the order of bank.repeat_interleave(g, 0) (beam search)
+ * Bv = B is the identity (every existing entry is that call with MMFS_BANK_TILE).  The result is, bit for bit, the same
+ * call on the expanded bank: only the (b, h) slab a query row reads from changes.  loc / attn / out keep the batch B.
+ * mmfs_msda_forward_shared: mmfs_msda_forward_flags with a shared bank (same routing, decided for the B query rows).
+ * MMFS_E_DIMS for Bv <= 0 or B % Bv != 0, MMFS_E_UNSUPPORTED for another layout code.  Forward only: a backward on a shared
+ * bank is the backward on the expanded bank with grad_value summed over the copies (the Python shim does that).
+ */
+#define MMFS_BANK_TILE 0
+#define MMFS_BANK_INTERLEAVE 1
+int mmfs_msda_forward_shared(int dtype,
+                             const void *value, const int64_t *shapes, const int64_t *start,
+                             const void *loc, const void *attn, void *out,
+                             int64_t B, int64_t Bv, int layout, int64_t S, int64_t H, int64_t D,
+                             int64_t L, int64_t Nq, int64_t P, unsigned flags, void *stream);
 
 /* Flags of mmfs_msda_backward(). */
 #define MMFS_BWD_CANONICAL_LEVELS 1u
@@ -470,6 +493,19 @@ int mmfs_sample_forward_heads(int dtype, const void *value, const int64_t *shape
                               void *out, float *sink,
                               int64_t N, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L, int64_t P, int64_t n,
                               int64_t M, int64_t Lr, int64_t Nr, void *stream);
+
+/* The same with a shared bank (see mmfs_msda_forward_shared): ``value`` [Nv, S, H, D] serves the N = g * Nv query rows of
+ * off_q / att_q / relpos / out / sink (and ref when it is batched) in the ``layout`` order, MMFS_BANK_TILE or
+ * MMFS_BANK_INTERLEAVE; MMFS_E_DIMS for Nv <= 0 or N % Nv != 0.  ``out`` is bit-identical to the call on the expanded bank.
+ * The launch order is the unshared call's: launching the g query rows of one bank row next to each other measured no faster
+ * (DESIGN.md 4.9). */
+int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
+                                     const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                                     const void *off_tab, const void *att_tab,
+                                     const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                                     void *out, float *sink,
+                                     int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                                     int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream);
 
 /* How many lane groups share ONE query's samples in mmfs_sample_forward* for this shape (``nL`` = n * L level rows):
  * 1 = the samples are summed in their order, ``out`` bit-identical to mmfs_plan_forward + mmfs_msda_forward;

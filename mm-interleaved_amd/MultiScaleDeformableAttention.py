@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 __all__ = ["ms_deform_attn_forward", "ms_deform_attn_backward", "register_level_tables", "library_path",
-           "build_info", "check_level_table_status"]
+           "build_info", "check_level_table_status", "value_row_map"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("MMFS_MSDA_LIB", os.path.join(_HERE, "libmmfs_msda.so"))
@@ -40,7 +40,7 @@ if not os.path.exists(_LIB_PATH):
 
 _lib = ctypes.CDLL(_LIB_PATH)
 
-_ABI_VERSION = 13
+_ABI_VERSION = 14
 _i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
 _lib.mmfs_msda_abi_version.restype = _int
@@ -53,6 +53,8 @@ _lib.mmfs_msda_forward.restype = _int
 _lib.mmfs_msda_forward.argtypes = [_int] + [_vp] * 6 + [_i64] * 7 + [_vp]
 _lib.mmfs_msda_forward_flags.restype = _int
 _lib.mmfs_msda_forward_flags.argtypes = [_int] + [_vp] * 6 + [_i64] * 7 + [ctypes.c_uint, _vp]
+_lib.mmfs_msda_forward_shared.restype = _int
+_lib.mmfs_msda_forward_shared.argtypes = [_int] + [_vp] * 6 + [_i64] * 2 + [_int] + [_i64] * 6 + [ctypes.c_uint, _vp]
 _lib.mmfs_msda_backward.restype = _int
 _lib.mmfs_msda_backward.argtypes = [_int] + [_vp] * 10 + [_i64] * 8 + [ctypes.c_uint, _vp]
 _lib.mmfs_msda_backward_checked.restype = _int
@@ -168,6 +170,39 @@ def _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):
     return B, S, H, D, L, Nq, P
 
 
+# How a bank of batch Bv serves a query batch B = g * Bv (include/mmfs_msda.h, MMFS_BANK_*): query row b reads bank row
+# (b / div) % Bv, div = 1 for "tile" (the order of torch.cat([bank] * g): classifier-free guidance) and g for "interleave"
+# (the order of bank.repeat_interleave(g, 0): beam search).
+_VALUE_REPEAT = {"tile": 0, "interleave": 1}
+
+
+def value_row_map(B, Bv, value_repeat):
+    """The bank row each of the B query rows reads (a list of ints): what the kernels compute, on the host."""
+    _require(value_repeat in _VALUE_REPEAT, f"value_repeat must be None, 'tile' or 'interleave', not {value_repeat!r}")
+    _require(Bv > 0 and B % Bv == 0, f"value_repeat={value_repeat!r}: the bank's batch ({Bv}) must divide the query batch ({B})")
+    div = 1 if value_repeat == "tile" else B // Bv
+    return [(b // div) % Bv for b in range(B)]
+
+
+def _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, value_repeat):
+    """``_dims`` for a bank of batch Bv = value.shape[0] shared by the B = sampling_loc.shape[0] query rows:
+    (B, S, H, D, L, Nq, P, Bv)."""
+    _require(value_repeat in _VALUE_REPEAT, f"value_repeat must be None, 'tile' or 'interleave', not {value_repeat!r}")
+    if value.dim() != 4 or sampling_loc.dim() != 6:
+        return _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight) + (value.shape[0],)
+    Bv, B = value.shape[0], sampling_loc.shape[0]
+    _require(Bv > 0 and B % Bv == 0, f"value_repeat={value_repeat!r}: the bank's batch ({Bv}) must divide the query batch ({B})")
+    # (the other checks against the expanded bank's shape, on a tensor without storage)
+    shape_only = torch.empty((B,) + tuple(value.shape[1:]), device="meta")
+    return _dims(shape_only, spatial_shapes, level_start_index, sampling_loc, attn_weight) + (Bv,)
+
+
+def _expand_bank(value, B, value_repeat):
+    """The bank as ``g`` explicit copies in the query order: what a shared call is defined against."""
+    g = B // value.shape[0]
+    return value.repeat(g, *([1] * (value.dim() - 1))) if value_repeat == "tile" else value.repeat_interleave(g, 0)
+
+
 def _same_dtype(value, sampling_loc, attn_weight):
     """The reference reads all three through one scalar_t (.cu:67-73).  softmax under
     autocast may hand an fp32 attn_weight next to fp16 values; cast instead of reading
@@ -274,28 +309,41 @@ def check_level_table_status(device=None, synchronize=False):
 
 
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                           im2col_step):
-    """Reference: ms_deform_attn_cuda_forward, src/cuda/ms_deform_attn_cuda.cu:21-81."""
+                           im2col_step, *, value_repeat=None):
+    """Reference: ms_deform_attn_cuda_forward, src/cuda/ms_deform_attn_cuda.cu:21-81.
+    ``value_repeat`` (an addition): None, or "tile" / "interleave" when ``value`` [Bv, S, H, D] is a bank shared by the
+    B = g * Bv query rows of ``sampling_loc`` -- query row b reads bank row b % Bv ("tile", the order of
+    ``torch.cat([value] * g)``) or b // g ("interleave", of ``value.repeat_interleave(g, 0)``).  The result is the op on
+    the expanded bank, bit for bit; the copy is never made (mmfs_msda_forward_shared)."""
     _require(isinstance(value, torch.Tensor) and value.is_cuda, "Not implemented on the CPU")
     if _status_words:
         check_level_table_status()
     _validate([("value", value), ("spatial_shapes", spatial_shapes),
                ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                ("attn_weight", attn_weight)], value)
-    B, S, H, D, L, Nq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+    if value_repeat is None:
+        B, S, H, D, L, Nq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+    else:
+        B, S, H, D, L, Nq, P, Bv = _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                value_repeat)
     step = min(B, int(im2col_step)) if B > 0 else 1
     _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
     sampling_loc, attn_weight = _same_dtype(value, sampling_loc, attn_weight)
     value = _aligned(value)
     out = torch.empty((B, Nq, H * D), dtype=value.dtype, device=value.device)
     code = _DTYPE_CODE[value.dtype]
-    dims = (B, S, H, D, L, Nq, P)
     with _on_device(value.device):
         stream = _stream(value.device)
-        status = _launch(
-            "msda_fwd", value.device, _lib.mmfs_msda_forward_flags, code, value.data_ptr(), spatial_shapes.data_ptr(),
-            level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-            out.data_ptr(), *dims, _FWD_FLAGS[_fwd_algo], stream)
+        if value_repeat is None:
+            status = _launch(
+                "msda_fwd", value.device, _lib.mmfs_msda_forward_flags, code, value.data_ptr(), spatial_shapes.data_ptr(),
+                level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                out.data_ptr(), B, S, H, D, L, Nq, P, _FWD_FLAGS[_fwd_algo], stream)
+        else:
+            status = _launch(
+                "msda_fwd", value.device, _lib.mmfs_msda_forward_shared, code, value.data_ptr(), spatial_shapes.data_ptr(),
+                level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                out.data_ptr(), B, Bv, _VALUE_REPEAT[value_repeat], S, H, D, L, Nq, P, _FWD_FLAGS[_fwd_algo], stream)
     _check(status, "ms_deform_attn_forward")
     return out
 
@@ -441,13 +489,31 @@ def register_level_tables(spatial_shapes, level_start_index, S, host_shapes=None
 
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                            grad_output, im2col_step, lazy_zero_attn=False):
+                            grad_output, im2col_step, lazy_zero_attn=False, *, value_repeat=None):
     """Reference: ms_deform_attn_cuda_backward, src/cuda/ms_deform_attn_cuda.cu:84-166.
     Returns [grad_value, grad_sampling_loc, grad_attn_weight] shaped and typed like the
     corresponding inputs.  ``lazy_zero_attn`` (an addition, MMFS_BWD_LAZY_ZERO_ATTN): the caller
     never reads grad_attn_weight where attn_weight is exactly 0 (MMFS's masked softmax multiplies it
-    by the weight), so those entries may come back as 0 without their value rows being read."""
+    by the weight), so those entries may come back as 0 without their value rows being read.
+    ``value_repeat`` (another, see ``ms_deform_attn_forward``): a shared bank.  Correct and deterministic, NOT fast --
+    sharing is for generation, not training: the backward above runs on the expanded bank (the g copies are made inside
+    the call) and grad_value [Bv, S, H, D] is the sum over the copies (``view(...).sum(dim)``), bit for bit what autograd
+    returns through ``value.expand``."""
     _require(isinstance(value, torch.Tensor) and value.is_cuda, "Not implemented on the CPU")
+    if value_repeat is not None:
+        _validate([("value", value), ("sampling_loc", sampling_loc)], value)
+        B, S, H, D, L, Nq, P, Bv = _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                value_repeat)
+        g = B // Bv
+        grad_value, grad_loc, grad_attn = ms_deform_attn_backward(
+            _expand_bank(value, B, value_repeat), spatial_shapes, level_start_index, sampling_loc, attn_weight,
+            grad_output, im2col_step, lazy_zero_attn)
+        rest = grad_value.shape[1:]
+        if value_repeat == "tile":
+            grad_value = grad_value.view(g, Bv, *rest).sum(0)
+        else:
+            grad_value = grad_value.view(Bv, g, *rest).sum(1)
+        return [grad_value, grad_loc, grad_attn]
     if _status_words:
         check_level_table_status()
     _validate([("value", value), ("spatial_shapes", spatial_shapes),

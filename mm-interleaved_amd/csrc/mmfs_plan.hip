@@ -331,7 +331,7 @@ mmfs_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const bool q_ok = q < d.Nq;
     const int nL = d.L;                                   // = n * levels per image
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)bc.b * d.S) * HD + (int64_t)bc.h * d.D;
+    const T *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
     const uint32_t lane_off = (uint32_t)(lig * 16);
     const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)bc.h * d.D) * (int64_t)sizeof(T));
@@ -591,7 +591,7 @@ mmfs_sample_decode(const T *__restrict__ value, const int64_t *__restrict__ shap
     const int q = (blockIdx.x / d.H) % d.Nq, b = blockIdx.x / d.H / d.Nq;
     const int nL = d.L;
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)b * d.S) * HD + (int64_t)h * d.D;
+    const T *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
     const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(T));
     const float sink_logit = -logf((float)nL);
@@ -917,12 +917,28 @@ int mmfs_sample_forward_heads(int dtype, const void *value, const int64_t *shape
                               int64_t N, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L, int64_t P, int64_t n,
                               int64_t M, int64_t Lr, int64_t Nr, void *stream)
 {
+    // (an empty batch is a bank of one row's worth: nothing is read)
+    return mmfs_sample_forward_heads_shared(dtype, value, shapes, start, off_q, att_q, ld_off, ld_att, off_tab, att_tab, relpos,
+                                            ref, ratios, token, out, sink, N, N > 0 ? N : 1, MMFS_BANK_TILE, S, Lq, H, D, L, P,
+                                            n, M, Lr, Nr, stream);
+}
+
+int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
+                                     const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                                     const void *off_tab, const void *att_tab,
+                                     const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                                     void *out, float *sink,
+                                     int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                                     int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream)
+{
     using namespace mmfs;
     const int es = esize(dtype);
     if (!es) return MMFS_E_DTYPE;
     PlanDims pd;
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &pd);
     if (rc) return rc;
+    if (Nv <= 0 || N % Nv != 0) return MMFS_E_DIMS;
+    if (layout != MMFS_BANK_TILE && layout != MMFS_BANK_INTERLEAVE) return MMFS_E_UNSUPPORTED;
     if (S < 0 || D <= 0 || S > 0x7ffffffdLL || H * D > 0x7fffffffLL) return MMFS_E_DIMS;
     if (N * Lq * H == 0) return MMFS_OK;
     if (P == 16 || S == 0) return MMFS_E_UNSUPPORTED;                       // (P = 16: the two-kernel path)
@@ -945,6 +961,8 @@ int mmfs_sample_forward_heads(int dtype, const void *value, const int64_t *shape
     Dims d;
     d.B = (int)N; d.S = (int)S; d.H = (int)H; d.D = (int)D; d.L = (int)(n * L); d.Nq = (int)Lq; d.P = (int)P;
     d.K = d.L * d.P; d.lazy_attn = 0; d.blocks4 = 0;
+    d.Bv = (int)Nv;                                                         // (Nv = N: the unshared call)
+    d.vdiv = layout == MMFS_BANK_INTERLEAVE ? (int)(N / Nv) : 1;
     int G = 4;
     while (G < d.L) G *= 2;                                                 // the plan kernel's lane-group width
     hipStream_t st = (hipStream_t)stream;

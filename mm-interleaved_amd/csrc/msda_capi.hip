@@ -42,6 +42,8 @@ int make_dims(int64_t B, int64_t S, int64_t H, int64_t D, int64_t L, int64_t Nq,
     d->taps_algo = 0;
     d->taps_sorted = 0;
     d->tiles_hint = 0;
+    d->Bv = (int)B;
+    d->vdiv = 1;
     return MMFS_OK;
 }
 
@@ -86,11 +88,27 @@ int mmfs_msda_forward_flags(int dtype, const void *value, const int64_t *shapes,
                             int64_t B, int64_t S, int64_t H, int64_t D, int64_t L, int64_t Nq, int64_t P,
                             unsigned flags, void *stream)
 {
+    // (an empty batch is a bank of one row's worth: nothing is read)
+    return mmfs_msda_forward_shared(dtype, value, shapes, start, loc, attn, out, B, B > 0 ? B : 1, MMFS_BANK_TILE, S, H, D, L,
+                                    Nq, P, flags, stream);
+}
+
+int mmfs_msda_forward_shared(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
+                             const void *loc, const void *attn, void *out,
+                             int64_t B, int64_t Bv, int layout, int64_t S, int64_t H, int64_t D, int64_t L, int64_t Nq,
+                             int64_t P, unsigned flags, void *stream)
+{
     const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     mmfs::Dims d;
     const int rc = make_dims(B, S, H, D, L, Nq, P, &d);
     if (rc) return rc;
+    if (Bv <= 0 || B % Bv != 0) return MMFS_E_DIMS;
+    if (layout != MMFS_BANK_TILE && layout != MMFS_BANK_INTERLEAVE) return MMFS_E_UNSUPPORTED;
+    if (B > 0) {
+        d.Bv = (int)Bv;
+        d.vdiv = layout == MMFS_BANK_INTERLEAVE ? (int)(B / Bv) : 1;
+    }
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_out = B * Nq * H * D;
     if (n_out == 0) return MMFS_OK;

@@ -23,7 +23,13 @@ struct Dims {
     int tiles_hint;          // backward: sort tiles of all levels when the caller knows the level table on the host (else 0: a bound is launched)
     int taps_sorted;         // backward: grad_loc / grad_attn come from the cell-sorted records too (msda_bwd_taps_sorted.hip): the sort keeps
                              // zero-weight samples (unless lazy_attn), its records carry query * P + point, it zeroes the gradients of samples without a record
+    // forward, shared bank (include/mmfs_msda.h, MMFS_BANK_*): value has Bv rows and query row b reads bank row (b / vdiv) % Bv --
+    // vdiv = 1 "tile", B / Bv "interleave".  An unshared call has Bv = B, vdiv = 1 (value_row is then b itself)
+    int Bv, vdiv;
 };
+
+// the bank row a query row's (b, h) slab is read from
+__device__ __forceinline__ int value_row(const Dims &d, int b) { return d.Bv == d.B ? b : (b / d.vdiv) % d.Bv; }
 
 // ---------------------------------------------------------------- storage types
 typedef _Float16 half_t;

@@ -70,7 +70,7 @@ msda_fwd_vec(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int Ksel = d.K;
 
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)bc.b * d.S) * HD + (int64_t)bc.h * d.D;   // this (b, h)
+    const T *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;   // this (b, h)
     const T *vbase = slab + lig * VEC;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
     const uint32_t lane_off = (uint32_t)(lig * 16);
@@ -256,7 +256,7 @@ msda_fwd_scalar(const T *__restrict__ value, const int64_t *__restrict__ shapes,
         const int64_t item = idx / d.D;                 // (b*Nq + q)*H + h
         const int h = (int)(item % d.H);
         const int64_t b = item / d.H / d.Nq;
-        const T *vb = value + b * d.S * HD + (int64_t)h * d.D + c;
+        const T *vb = value + (int64_t)value_row(d, (int)b) * d.S * HD + (int64_t)h * d.D + c;
         A acc = 0;
         for (int k = 0; k < d.K; ++k) {
             const int l = k / d.P;

@@ -94,7 +94,7 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int tq = run / d.H;
     const int q_wg0 = (tq % d.q_tiles) * q_per_wg;
     const int b = tq / d.q_tiles;
-    const T *slab = value + ((int64_t)b * d.S) * HD + (int64_t)h * d.D;
+    const T *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
     const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(T));
 
     // ---- from here on every wave works on its own

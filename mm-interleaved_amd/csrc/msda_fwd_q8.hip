@@ -279,7 +279,7 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
     const int sl = t % n_slices; t /= n_slices;
     const int q_run0 = (t % d.q_tiles) * q_per_run;
     const int b = t / d.q_tiles;
-    const T *slab = value + ((int64_t)b * d.S) * HD + (int64_t)h * d.D + sl * kCS;
+    const T *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D + sl * kCS;
     const __amdgpu_buffer_rsrc_t rsrc =
         make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D - sl * kCS) * (int64_t)sizeof(T));
     const int q_run1 = min(d.Nq, q_run0 + q_per_run);

@@ -210,7 +210,7 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int tq = run / d.H;
     const int q_wg0 = (tq % d.q_tiles) * q_per_wg;
     const int b = tq / d.q_tiles;
-    const T *slab = value + ((int64_t)b * d.S) * HD + (int64_t)h * d.D;
+    const T *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
     const int64_t slab_bytes = ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(T);
     const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, slab_bytes);
     // (the same descriptor as four words, for the image fill's assembly: base, stride 0, extent, raw 32-bit data format)

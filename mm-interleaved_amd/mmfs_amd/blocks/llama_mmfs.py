@@ -105,22 +105,25 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
         self._gate_fold = FoldedLinear()
 
     def forward(self, hidden_states, vision_hidden_states=None, cross_attention_mask=None, value=None, image_ranks=None,
-                residual=None):
+                residual=None, bank_repeat=None):
         """hidden_states [B, Lq, hidden]; vision_hidden_states [B, n, sum hw, image_embed_dim];
         cross_attention_mask [B, Lq', n] (float, 1 = visible) -> [B, Lq, hidden].
         ``value`` (an addition): this layer's ``value_proj(norm2(vision_hidden_states))`` [B, n, sum hw, d_inner] as
         a ``LlamaMMFSSchedule`` projected it for all layers at once; the bank is then only looked at for its shape.
         ``image_ranks`` (another): ``LlamaMMFSSchedule.image_ranks(cross_attention_mask, Lq)``, made once per step.
         ``residual`` (a third) [B, Lq, hidden]: the result is ``residual + layer(...)`` -- the decoder layer's own next
-        statement (modeling_llama_mmfs.py:700-717), which without gradients rides in the output projection's kernel."""
-        args = (hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual)
+        statement (modeling_llama_mmfs.py:700-717), which without gradients rides in the output projection's kernel.
+        ``bank_repeat`` (a fourth, ``MMFS.forward``): None, or "interleave" / "tile" when ``vision_hidden_states`` / ``value``
+        have the batch Bv of a bank shared by the B = g * Bv token rows -- beam search hands the un-expanded bank (HF's
+        ``repeat_interleave(num_beams, 0)`` order: "interleave")."""
+        args = (hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual, bank_repeat)
         if self.graph_training_calls and self.training:
             # a training step's call as HIP graphs once its shapes have been seen a few times (mmfs_amd/graphed.py) -- the
             # forward with its saved activations, the backward; and the no-grad forward of a checkpointing caller
             return graphed_call(self, self._forward, args, recompute=False, plain=lambda: self._forward(*args))
         return self._forward(*args)
 
-    def _forward(self, hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual):
+    def _forward(self, hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual, bank_repeat=None):
         hidden_states = self.norm1(hidden_states)
         if value is None:
             vision_hidden_states = self.norm2(vision_hidden_states)
@@ -135,16 +138,17 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
             return self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                              input_spatial_shapes=shapes, input_level_start_index=start, input_padding_mask=None,
                              attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
-                             output_weights=folded, output_residual=residual)
+                             output_weights=folded, output_residual=residual, bank_repeat=bank_repeat)
         if residual is not None:
             # the gate and the residual sum ride with the output projection (``GatedProjectionFunction`` with gradients)
             return self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                              input_spatial_shapes=shapes, input_level_start_index=start, input_padding_mask=None,
                              attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
-                             output_gate=self._gate(), output_residual=residual)
+                             output_gate=self._gate(), output_residual=residual, bank_repeat=bank_repeat)
         out = self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                         input_spatial_shapes=shapes, input_level_start_index=start,
-                        input_padding_mask=None, attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks)
+                        input_padding_mask=None, attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
+                        bank_repeat=bank_repeat)
         return out * self._gate()
 
     def _gate(self):
@@ -163,8 +167,9 @@ class ProjectedBank:
     """``value_proj_k(norm2_k(bank))`` of every MMFS layer of a decoder for one feature bank: ``values[k]`` is
     layer k's [B, n, sum hw, d_inner] (contiguous).  Made by ``LlamaMMFSSchedule.project``."""
 
-    def __init__(self, values, bank, source=None, weights=None):
+    def __init__(self, values, bank, source=None, weights=None, bank_repeat=None):
         self.values, self.bank = values, bank
+        self.bank_repeat = bank_repeat                   # how the caller said the bank serves its token rows (``project``)
         self.source, self.weights = source, weights      # identity cache: (tensor, version), parameter signature
 
     def matches(self, bank, weights):
@@ -231,17 +236,23 @@ class LlamaMMFSSchedule:
             y = y + torch.stack([l.attn.value_proj.bias for l in self.layers])[:, None, :]
         return [y[k].view(*bank.shape[:-1], -1) for k in range(len(self.layers))]
 
-    def project(self, vision_hidden_states):
-        """[B, n, sum hw, image_embed_dim] -> ``ProjectedBank`` (kept across calls outside autograd)."""
+    def project(self, vision_hidden_states, bank_repeat=None):
+        """[B, n, sum hw, image_embed_dim] -> ``ProjectedBank`` (kept across calls outside autograd).  ``bank_repeat``:
+        None, or "interleave" / "tile" when the bank is the un-expanded one of beam search / guidance: the projections are
+        made for its own rows (fewer than the token batch) and the layers are then called with
+        ``bank_repeat=projected.bank_repeat``."""
+        if bank_repeat not in (None, "tile", "interleave"):
+            raise ValueError(f"bank_repeat must be None, 'tile' or 'interleave', not {bank_repeat!r}")
         if not self.can_fuse():         # the reference's schedule, layer by layer
             return ProjectedBank([l.attn.value_proj(l.norm2(vision_hidden_states)) for l in self.layers],
-                                 vision_hidden_states)
+                                 vision_hidden_states, bank_repeat=bank_repeat)
         keep = self.cache_projected_bank and not torch.is_grad_enabled() and not any(l.training for l in self.layers)
         sig = self._weights()
-        if keep and self._projected is not None and self._projected.matches(vision_hidden_states, sig):
+        if (keep and self._projected is not None and self._projected.matches(vision_hidden_states, sig)
+                and self._projected.bank_repeat == bank_repeat):
             return self._projected
         proj = ProjectedBank(self._project(vision_hidden_states), vision_hidden_states,
-                             (vision_hidden_states, tensor_version(vision_hidden_states)), sig)
+                             (vision_hidden_states, tensor_version(vision_hidden_states)), sig, bank_repeat=bank_repeat)
         self._projected = proj if keep else None
         return proj
 

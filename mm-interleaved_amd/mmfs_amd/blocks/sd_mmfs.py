@@ -205,7 +205,8 @@ class MMFSBlock(CacheInvalidation, nn.Module):
                 and n.bias.dtype == sample.dtype and self.pos_embed.dtype == sample.dtype
                 and self._conv_is_pointwise() and layout_supported(sample))
 
-    def _inner(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None):
+    def _inner(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None,
+               bank_repeat=None):
         B, C, H, W = sample.shape
         if value is None and normed is not None:
             # the bank already normalised WITHOUT the affine (MMFSNet, shared by its blocks): this block's affine folds
@@ -236,7 +237,7 @@ class MMFSBlock(CacheInvalidation, nn.Module):
             folded = self._conv_fold.get(proj.weight, proj.bias, self.conv.weight.view(C, C), self.conv.bias)
         out = self.mmfs(query, ref, self.feat_norm(ms_feat) if value is None else ms_feat, shapes, start,
                         input_padding_mask=None, attention_mask=ms_feat_mask, value=value, image_ranks=image_ranks,
-                        output_weights=folded)
+                        output_weights=folded, bank_repeat=bank_repeat)
         # the zero-initialised 1x1 convolution (sd_mmfs.py:88-94, 146) is a per-token linear map:
         # applied on the token-major tensor it is one GEMM each way (the convolution library's 1x1
         # backward took 0.45 ms per block at B=8, the GEMMs take ~0.05)
@@ -252,7 +253,8 @@ class MMFSBlock(CacheInvalidation, nn.Module):
             out = self.conv(out.transpose(1, 2).reshape(B, C, H, W))
         return out if residual is None else residual + out
 
-    def forward(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None):
+    def forward(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None,
+                bank_repeat=None):
         """sample [B, C_q, H, W]; ms_feat [B, n, sum_l H_l*W_l, C_v]; ms_feat_mask [B, n];
         spatial_shapes: the levels of ONE image, list of (H_l, W_l)  ->  [B, C_q, H, W].
         ``value`` (an addition to sd_mmfs.py:121-146): this block's
@@ -261,7 +263,9 @@ class MMFSBlock(CacheInvalidation, nn.Module):
         ``residual`` (another): a [B, C_q, H, W] tensor the result is added to -- the add ``MMFSNet`` does with every
         block's output (sd_mmfs.py:262-270), here so that it can share the pass that restores the layout; ``normed``
         (another): ``layer_norm(ms_feat)`` without the affine, when the caller has it -- the block then folds its
-        ``feat_norm`` affine into its value projection (inside its checkpoint: the projected bank is not kept)."""
+        ``feat_norm`` affine into its value projection (inside its checkpoint: the projected bank is not kept);
+        ``bank_repeat`` (another, ``MMFS.forward``): ``ms_feat`` / ``value`` / ``normed`` are a bank of batch Bv shared by the
+        B = g * Bv rows of ``sample`` / ``ms_feat_mask`` -- "tile" (classifier-free guidance) or "interleave"."""
         spatial_shapes = [tuple(int(v) for v in s) for s in spatial_shapes]
         if self.gradient_checkpointing and self.training:
             # the op is stateless and re-entrant: the forward is simply re-run in backward
@@ -271,7 +275,7 @@ class MMFSBlock(CacheInvalidation, nn.Module):
             # trip that a HIP-graph capture of the step refuses)
             def plain():
                 return cp.checkpoint(self._inner, sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks, residual,
-                                     normed, use_reentrant=False, preserve_rng_state=False)
+                                     normed, bank_repeat, use_reentrant=False, preserve_rng_state=False)
             if self.graph_checkpoints:
                 keep = self.graph_keeps_activations
                 if keep == "auto":
@@ -285,18 +289,21 @@ class MMFSBlock(CacheInvalidation, nn.Module):
                         else:
                             keep = self.__dict__["_keeps_latched"] = bool(memory_is_plentiful(sample.device))
                 return graphed_call(self, self._inner, (sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks,
-                                                        residual, normed), recompute=not keep, plain=plain)
+                                                        residual, normed, bank_repeat), recompute=not keep, plain=plain)
             return plain()
-        return self._inner(sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks, residual, normed)
+        return self._inner(sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks, residual, normed, bank_repeat)
 
 
 class ProjectedFeatures:
     """``value_proj(feat_norm(bank))`` of every block of an ``MMFSNet`` for one feature bank:
     ``values[k]`` is block k's [B, n, sum_l H_l*W_l, d_inner] (the mid block last).  Made by
-    ``MMFSNet.project_features``; accepted by ``MMFSNet.forward`` in place of the feature list."""
+    ``MMFSNet.project_features``; accepted by ``MMFSNet.forward`` in place of the feature list.  ``bank_repeat``: None,
+    or "tile" when the projections hold the first half of a bank whose two halves were equal (``dedupe_repeated_bank``):
+    ``MMFSNet.forward`` then serves the doubled batch from them."""
 
-    def __init__(self, values, bank, shapes, sources=None, weights=None):
+    def __init__(self, values, bank, shapes, sources=None, weights=None, bank_repeat=None):
         self.values, self.bank, self.shapes = values, bank, shapes
+        self.bank_repeat = bank_repeat
         # what it was computed from (identity cache of MMFSNet.forward): the feature tensors with
         # their versions, and (storage, version) of every parameter that went in
         self.sources, self.weights = sources, weights
@@ -329,6 +336,12 @@ class MMFSNet(CacheInvalidation, nn.Module):
     # a bank of many images, the step falls back to recomputing inside the checkpoints instead of running out of memory.
     project_once_in_training = "auto"
     project_once_budget = 0.125
+    # Opt-in for the unchanged reference pipeline, whose classifier-free guidance hands a bank of two equal halves
+    # (``torch.cat([ms_feat] * 2)``, sd_pipeline_monkey_patch.py:172-178): in eval mode without gradients, an even feature
+    # batch is compared half against half (``torch.equal`` per level) when it is projected -- once per bank, the projection
+    # cache then holds it -- and if the halves are equal only the first half is projected and the blocks run with
+    # ``bank_repeat="tile"``.  Off by default: fewer projected rows may select another GEMM kernel (other roundings).
+    dedupe_repeated_bank = False
 
     def _project_once(self, mmfs_features):
         """Whether this training step keeps all blocks' projections of the bank (see ``project_once_in_training``)."""
@@ -406,15 +419,31 @@ class MMFSNet(CacheInvalidation, nn.Module):
                    and type(b.mmfs.value_proj) is nn.Linear and hook_free(b.mmfs.value_proj) and hook_free(b.feat_norm)
                    for b in blocks)
 
-    def project_features(self, mmfs_features):
+    def project_features(self, mmfs_features, dedupe=False):
         """Per level [B, n, C, h_l, w_l] -> ``ProjectedFeatures``: the bank normalised ONCE, then
-        every block's value projection with its LayerNorm affine folded into the weights."""
+        every block's value projection with its LayerNorm affine folded into the weights.  ``dedupe``: when B is even and
+        every level's two halves are equal, project the first half only (``bank_repeat = "tile"``; see
+        ``dedupe_repeated_bank``)."""
+        sources = [(f, tensor_version(f)) for f in mmfs_features]
+        repeat = None
+        if dedupe and self._halves_equal(mmfs_features):
+            mmfs_features = [f[:f.shape[0] // 2] for f in mmfs_features]
+            repeat = "tile"
         shapes = [(f.shape[-2], f.shape[-1]) for f in mmfs_features]
         bank = self._pack(mmfs_features)
         norm = self.mmfs_mid_block.feat_norm
         xhat = F.layer_norm(bank, norm.normalized_shape, None, None, norm.eps)
-        return ProjectedFeatures(self._project_all(xhat), bank, shapes, [(f, tensor_version(f)) for f in mmfs_features],
-                                 self._projection_weights())
+        return ProjectedFeatures(self._project_all(xhat), bank, shapes, sources, self._projection_weights(), bank_repeat=repeat)
+
+    @staticmethod
+    def _halves_equal(mmfs_features):
+        """Whether every level of the bank is two equal halves along the batch (a host round trip: once per bank)."""
+        B = int(mmfs_features[0].shape[0])
+        if B < 2 or B % 2 or any(int(f.shape[0]) != B for f in mmfs_features):
+            return False
+        if mmfs_features[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            return False
+        return all(torch.equal(f[:B // 2], f[B // 2:]) for f in mmfs_features)
 
     def _project_all(self, xhat):
         """Every block's value projection of the normalised bank as ONE batched GEMM, [tokens, C] x [n_blocks, C, d_inner]
@@ -449,10 +478,14 @@ class MMFSNet(CacheInvalidation, nn.Module):
         self.__dict__.pop("_projected", None)
         self.clear_caches()
 
-    def forward(self, sample, down_block_res_samples, mmfs_features, mmfs_mask):
+    def forward(self, sample, down_block_res_samples, mmfs_features, mmfs_mask, bank_repeat=None):
         """sample: mid-block input; down_block_res_samples: the UNet's down residuals;
         mmfs_features: per level [B, n, C, h_l, w_l] (or a ``ProjectedFeatures``); mmfs_mask [B, n]
-        -> (sample', tuple of residuals')   (sd_mmfs.py:230-272)."""
+        -> (sample', tuple of residuals')   (sd_mmfs.py:230-272).
+        ``bank_repeat`` (an addition, ``MMFS.forward``): None, or "tile" / "interleave" when ``mmfs_features`` (or the
+        ``ProjectedFeatures``) have the batch Bv of a bank shared by the B = g * Bv rows of ``sample``, the residuals and
+        ``mmfs_mask`` -- classifier-free guidance hands the un-doubled features with "tile".  The projections (and the
+        kept-projection cache) then hold Bv rows."""
         assert len(down_block_res_samples) == len(self.mmfs_down_blocks)
         proj = mmfs_features if isinstance(mmfs_features, ProjectedFeatures) else None
         # Under gradient checkpointing the reference recomputes feat_norm + value_proj inside every block's
@@ -468,7 +501,8 @@ class MMFSNet(CacheInvalidation, nn.Module):
             keep = self.cache_projected_features and not torch.is_grad_enabled() and not self.training
             proj = self.__dict__.get("_projected") if keep else None
             if proj is None or not proj.matches(mmfs_features, self._projection_weights()):
-                proj = self.project_features(mmfs_features)
+                dedupe = self.dedupe_repeated_bank and bank_repeat is None and not self.training and not torch.is_grad_enabled()
+                proj = self.project_features(mmfs_features, dedupe=True) if dedupe else self.project_features(mmfs_features)
             if keep:
                 self.__dict__["_projected"] = proj
             else:
@@ -476,6 +510,8 @@ class MMFSNet(CacheInvalidation, nn.Module):
         normed = None
         if proj is not None:
             bank, shapes, values = proj.bank, proj.shapes, proj.values
+            if bank_repeat is None:
+                bank_repeat = proj.bank_repeat
         else:
             shapes = [(f.shape[-2], f.shape[-1]) for f in mmfs_features]
             bank = self._pack(mmfs_features)
@@ -488,8 +524,9 @@ class MMFSNet(CacheInvalidation, nn.Module):
                 normed = F.layer_norm(bank, norm.normalized_shape, None, None, norm.eps)
         # (the images' ranks among the visible ones depend on the mask only: once for the 13 blocks)
         ranks = self.mmfs_mid_block.mmfs._image_relpos(mmfs_mask, 1) if mmfs_mask.dim() == 2 else None
-        new_res = tuple(blk(r, bank, mmfs_mask, shapes, value=v, image_ranks=ranks, residual=r, normed=normed)
+        new_res = tuple(blk(r, bank, mmfs_mask, shapes, value=v, image_ranks=ranks, residual=r, normed=normed,
+                            bank_repeat=bank_repeat)
                         for r, blk, v in zip(down_block_res_samples, self.mmfs_down_blocks, values))
         sample = self.mmfs_mid_block(sample, bank, mmfs_mask, shapes, value=values[-1], image_ranks=ranks, residual=sample,
-                                     normed=normed)
+                                     normed=normed, bank_repeat=bank_repeat)
         return sample, new_res

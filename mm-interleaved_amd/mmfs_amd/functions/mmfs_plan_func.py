@@ -28,6 +28,9 @@ _lib.mmfs_sample_forward_token.restype = _int
 _lib.mmfs_sample_forward_token.argtypes = [_int] + [_vp] * 13 + [_i64] * 11 + [_vp]
 _lib.mmfs_sample_forward_heads.restype = _int
 _lib.mmfs_sample_forward_heads.argtypes = [_int] + [_vp] * 5 + [_i64] * 2 + [_vp] * 8 + [_i64] * 11 + [_vp]
+_lib.mmfs_sample_forward_heads_shared.restype = _int
+_lib.mmfs_sample_forward_heads_shared.argtypes = ([_int] + [_vp] * 5 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
+                                                  + [_i64] * 10 + [_vp])
 _lib.mmfs_plan_forward_heads.restype = _int
 _lib.mmfs_plan_forward_heads.argtypes = [_int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 7 + [_i64] * 9 + [_vp]
 _lib.mmfs_plan_backward_heads.restype = _int
@@ -177,19 +180,31 @@ def sample_forward_groups(dtype, Lq, D, nL, P):
     return int(_lib.mmfs_sample_forward_groups(_CODE[dtype], Lq, D, nL, P)) if dtype in _CODE else 0
 
 
-def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, relpos, ref, ratios, H, L, P, token=None):
+def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, relpos, ref, ratios, H, L, P, token=None,
+                        value_repeat=None):
     """Plan -> sampler in ONE kernel (``mmfs_sample_forward`` in include/mmfs_msda.h):
     the locations / weights [N, Lq, H, n*L, P(, 2)] are never written.  Inference only (no autograd graph);
     bit-identical to ``MMFSPlanFunction`` + ``MSDeformAttnFunction`` (decode-sized calls: the same products with the fp32
     sums in another order, see ``sample_forward_groups``).  value [N, S, H, D]; the other
     arguments as for ``MMFSPlanFunction``.  Returns (out [N, Lq, H*D], sink [N, Lq, H] fp32), or None when
     the shape is outside the fused kernel's range (the caller then runs the two kernels).  ``token`` [.., H, D]
-    (MMFS's ignore token): ``out + token * sink`` is formed inside the kernel, with the framework statement's roundings."""
+    (MMFS's ignore token): ``out + token * sink`` is formed inside the kernel, with the framework statement's roundings.
+    ``value_repeat`` None, or "tile" / "interleave": ``value`` [Nv, S, H, D] is a bank shared by the N = g * Nv query
+    rows of ``off_q`` (MSDA.ms_deform_attn_forward; C ABI ``mmfs_sample_forward_heads_shared``)."""
     dt = value.dtype
     if dt not in _CODE or off_q.dtype != dt or not value.is_cuda:
         return None
-    N, S, Hh, D = value.shape
+    Nv, S, Hh, D = value.shape
     Lq = off_q.shape[1]
+    if value_repeat is None:
+        if off_q.shape[0] != Nv:
+            return None                   # (the two kernels then refuse the mismatched batches with the op's message)
+        N = Nv
+    else:
+        N = off_q.shape[0]
+        MSDA._require(value_repeat in MSDA._VALUE_REPEAT and Nv > 0 and N % Nv == 0,
+                      f"value_repeat={value_repeat!r}: expected 'tile' or 'interleave' and a bank batch ({Nv}) that divides "
+                      f"the query batch ({N})")
     n, Lr, Nr, M = relpos.shape[-1], relpos.shape[1], ref.shape[0], off_tab.shape[0]
     value = value.contiguous()
     off_q, ld_off = _token_rows(off_q, 2 * P)
@@ -207,11 +222,19 @@ def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, re
             return None
         tok = MSDA._aligned(token.reshape(Hh, D).contiguous())
     with torch.cuda.device(dev):
-        rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads, _CODE[dt], value.data_ptr(),
-                          shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
-                          off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
-                          ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(), sink.data_ptr(),
-                          N, S, Lq, Hh, D, L, P, n, M, Lr, Nr, MSDA._stream(dev))
+        if value_repeat is None:
+            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads, _CODE[dt], value.data_ptr(),
+                              shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
+                              off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
+                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
+                              sink.data_ptr(), N, S, Lq, Hh, D, L, P, n, M, Lr, Nr, MSDA._stream(dev))
+        else:
+            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads_shared, _CODE[dt], value.data_ptr(),
+                              shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
+                              off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
+                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
+                              sink.data_ptr(), N, Nv, MSDA._VALUE_REPEAT[value_repeat], S, Lq, Hh, D, L, P, n, M, Lr, Nr,
+                              MSDA._stream(dev))
     if rc == MSDA._E_UNSUPPORTED:
         return None
     MSDA._check(rc, "mmfs_sample_forward")

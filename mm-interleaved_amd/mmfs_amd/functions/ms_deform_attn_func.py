@@ -24,15 +24,17 @@ class MSDeformAttnFunction(Function):
     @staticmethod
     @_fwd
     def forward(ctx, value, value_spatial_shapes, value_level_start_index,
-                sampling_locations, attention_weights, im2col_step, lazy_zero_attn=False):
+                sampling_locations, attention_weights, im2col_step, lazy_zero_attn=False, value_repeat=None):
         # ``lazy_zero_attn`` is an addition to the reference's six arguments (see
         # MSDA.ms_deform_attn_backward): set by MMFS, whose softmax backward never looks at the
-        # gradient of a weight that is exactly zero
+        # gradient of a weight that is exactly zero.  ``value_repeat`` another (MSDA.ms_deform_attn_forward):
+        # None, or "tile" / "interleave" when ``value`` is a bank of batch Bv shared by g * Bv query rows
         ctx.im2col_step = im2col_step
         ctx.lazy_zero_attn = bool(lazy_zero_attn)
+        ctx.value_repeat = value_repeat
         output = MSDA.ms_deform_attn_forward(
             value, value_spatial_shapes, value_level_start_index,
-            sampling_locations, attention_weights, ctx.im2col_step)
+            sampling_locations, attention_weights, ctx.im2col_step, value_repeat=value_repeat)
         ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index,
                               sampling_locations, attention_weights)
         return output
@@ -44,8 +46,9 @@ class MSDeformAttnFunction(Function):
         grad_output = grad_output.contiguous()
         value, shapes, start, loc, attn = ctx.saved_tensors
         grad_value, grad_loc, grad_attn = MSDA.ms_deform_attn_backward(
-            value, shapes, start, loc, attn, grad_output, ctx.im2col_step, ctx.lazy_zero_attn)
-        return grad_value, None, None, grad_loc, grad_attn, None, None
+            value, shapes, start, loc, attn, grad_output, ctx.im2col_step, ctx.lazy_zero_attn,
+            value_repeat=ctx.value_repeat)
+        return grad_value, None, None, grad_loc, grad_attn, None, None, None
 
 
 def ms_deform_attn_core_pytorch(value, value_spatial_shapes, sampling_locations, attention_weights):

@@ -26,7 +26,8 @@ class GraphedMMFSNet:
     The results live in buffers owned by the graph and are overwritten by the next replay.
     Inference only (no autograd through a replay)."""
 
-    def __init__(self, net, sample, down_block_res_samples, mmfs_features, mmfs_mask, warmup=2):
+    def __init__(self, net, sample, down_block_res_samples, mmfs_features, mmfs_mask, warmup=2, bank_repeat=None):
+        # (``bank_repeat``: as ``MMFSNet.forward`` -- the features are a bank shared by the rows of ``sample``)
         assert isinstance(net, MMFSNet) and sample.is_cuda
         assert not net.training, "GraphedMMFSNet is inference only: net.eval() first (nothing is folded or kept in training mode)"
         self.net = net
@@ -40,11 +41,11 @@ class GraphedMMFSNet:
             side.wait_stream(torch.cuda.current_stream(sample.device))
             with torch.cuda.stream(side):          # first calls fill the caches (level tables, position tables)
                 for _ in range(warmup):
-                    net(self._sample, self._res, proj, self._mask)
+                    net(self._sample, self._res, proj, self._mask, bank_repeat=bank_repeat)
             torch.cuda.current_stream(sample.device).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self._out = net(self._sample, self._res, proj, self._mask)
+                self._out = net(self._sample, self._res, proj, self._mask, bank_repeat=bank_repeat)
             # The recorded kernels read the blocks' kept artefacts (folded weights, parameter-only tables, position
             # tables) at the addresses they had during the capture: hold them, so that an invalidation of the modules'
             # caches (a mode change, a state-dict load, ``invalidate_caches()``) cannot free what the graph replays.

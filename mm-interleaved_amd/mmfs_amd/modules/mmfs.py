@@ -230,10 +230,10 @@ class MMFS(CacheInvalidation, nn.Module):
         return res
 
     def sampling_plan(self, query, reference_points, input_spatial_shapes, attention_mask, n_images, sampler=None,
-                      image_ranks=None):
+                      image_ranks=None, bank_repeat=None):
         """Everything between the query and the op: sampling locations [N,Lq,H,n*L,P,2],
         attention weights over the real points [N,Lq,H,n*L,P], and the summed sink weights
-        [N,Lq,H] (mmfs.py:154-163, 174-265)."""
+        [N,Lq,H] (mmfs.py:154-163, 174-265).  ``bank_repeat``: how the sampler's bank serves the query rows (forward)."""
         N, Lq, _ = query.shape
         H, L, P, n = self.n_heads, self.n_levels, self.n_points, n_images
         nL = n * L
@@ -278,7 +278,7 @@ class MMFS(CacheInvalidation, nn.Module):
                 # returns the op's output and the sink weights instead of loc / attn
                 # (``sampler[2]``: the ignore token, whose term the kernel then adds itself -- the sink weights come back None)
                 res = mmfs_sample_forward(sampler[0], input_spatial_shapes, sampler[1], *heads[:4], relpos,
-                                          heads[5], self._ratios32(), H, L, P, token=sampler[2])
+                                          heads[5], self._ratios32(), H, L, P, token=sampler[2], value_repeat=bank_repeat)
                 if res is not None:
                     return None, res[0], (res[1] if sampler[2] is None else None)
             loc, attn, sink_sum = MMFSPlanFunction.apply(off_q.contiguous(), att_q.contiguous(), *heads[2:])
@@ -353,7 +353,7 @@ class MMFS(CacheInvalidation, nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
                 input_level_start_index, input_padding_mask=None, attention_mask=None, value=None, image_ranks=None,
-                output_weights=None, output_residual=None, output_gate=None):
+                output_weights=None, output_residual=None, output_gate=None, bank_repeat=None):
         """Arguments and result as mmfs.py:120-141 (``value`` is an addition: the caller's own
         ``value_proj(input_flatten)`` [N, n, hw, d_inner], e.g. one an ``MMFSNet`` projected for
         all its blocks at once; ``input_flatten`` is then only looked at for its shape; ``image_ranks`` another: this
@@ -366,21 +366,33 @@ class MMFS(CacheInvalidation, nn.Module):
         query [N, Lq, d_query]; reference_points [N|1, Lq, 1|n*L, 2|4] in [0,1];
         input_flatten [N, n_images, sum_l H_l*W_l, d_value]; input_spatial_shapes [n*L, 2];
         input_level_start_index [n*L]; input_padding_mask [N, n, hw] or None;
-        attention_mask [N, n] or [N, Lq, n]  ->  [N, Lq, d_out]."""
+        attention_mask [N, n] or [N, Lq, n]  ->  [N, Lq, d_out].
+        ``bank_repeat`` (a sixth): None, or "tile" / "interleave" when ONE bank serves several query rows -- classifier-free
+        guidance's ``torch.cat([features] * 2)``, beam search's ``repeat_interleave(num_beams, 0)``: ``input_flatten`` /
+        ``value`` / ``input_padding_mask`` then have the bank's batch Nv and ``query``, ``reference_points`` (when batched)
+        and ``attention_mask`` the query batch N = g * Nv; query row b reads bank row b % Nv ("tile") or b // g
+        ("interleave").  The value projection runs on the Nv rows; the result is the module's on the expanded bank."""
         N, Lq, _ = query.shape
-        N, n, hw, _ = input_flatten.shape
+        if bank_repeat is None:
+            N, n, hw, _ = input_flatten.shape
+        else:
+            Nv, n, hw, _ = input_flatten.shape
+            if bank_repeat not in ("tile", "interleave") or Nv <= 0 or N % Nv:
+                raise ValueError(f"bank_repeat={bank_repeat!r}: expected 'tile' or 'interleave' and a bank batch ({Nv}) "
+                                 f"that divides the query batch ({N})")
         host = host_shapes(input_spatial_shapes)
         if host is not None:                      # the reference checks this on the device (sync)
             assert int((host[:, 0] * host[:, 1]).sum()) == n * hw, (host.tolist(), n * hw)
         assert input_spatial_shapes.shape[0] == n * self.n_levels
 
+        Nb = N if bank_repeat is None else Nv
         if value is None:
             value = self.value_proj(input_flatten)
         else:
-            assert value.shape == (N, n, hw, self.d_inner), (value.shape, (N, n, hw, self.d_inner))
+            assert value.shape == (Nb, n, hw, self.d_inner), (value.shape, (Nb, n, hw, self.d_inner))
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], 0.0)
-        value = value.reshape(N, n * hw, self.n_heads, self.d_inner // self.n_heads).contiguous()
+        value = value.reshape(Nb, n * hw, self.n_heads, self.d_inner // self.n_heads).contiguous()
 
         # no autograd graph wanted (sampling / decoding): plan and sampler run as one kernel, the locations
         # and weights never exist as tensors (csrc/mmfs_plan.hip, mmfs_sample_fwd); bit-identical output
@@ -391,7 +403,7 @@ class MMFS(CacheInvalidation, nn.Module):
         tok_in = self.ignore_token if (fuse and self.ignore_token.dtype == value.dtype) else None
         loc, attn, sink_w = self.sampling_plan(query, reference_points, input_spatial_shapes, attention_mask, n,
                                                sampler=(value, input_level_start_index, tok_in) if fuse else None,
-                                               image_ranks=image_ranks)
+                                               image_ranks=image_ranks, bank_repeat=bank_repeat)
         if loc is None:
             out = attn                            # (the fused kernel's result)
             if sink_w is None:                    # ... the ignore token's term included
@@ -399,8 +411,10 @@ class MMFS(CacheInvalidation, nn.Module):
         else:
             # (last argument: the softmax that made ``attn`` multiplies the gradient of every weight by the
             # weight itself, so the op need not compute it where the weight -- an invisible image -- is 0)
+            # (the map only when there is one: the op's unshared call keeps its argument list)
             out = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
-                                             loc.to(value.dtype).contiguous(), attn, self.im2col_step, True)
+                                             loc.to(value.dtype).contiguous(), attn, self.im2col_step, True,
+                                             *((bank_repeat,) if bank_repeat is not None else ()))
         # the sinks' share goes to the (frozen, zero-initialised) ignore token (mmfs.py:236-241, 274)
         tok = self.ignore_token.view(1, 1, self.n_heads, -1)
         if (out.is_cuda and torch.is_grad_enabled() and not torch.is_autocast_enabled() and tok.dtype == out.dtype
