@@ -13,10 +13,29 @@ allocates nothing, and never synchronises (tests/test_modules_gpu.py checks the 
 ``GraphedTrainingStep`` (round 4) does the same for a TRAINING step -- forward + backward recorded as one graph: the 13-block
 net's step is ~5 000 launches that the host issues in 37-39 ms while their kernels take under 30.
 """
+import contextlib
+import gc
+
 import torch
 
 from .blocks.llama_mmfs import LlamaMMFSSchedule, ProjectedBank
 from .blocks.sd_mmfs import MMFSNet, ProjectedFeatures
+
+
+@contextlib.contextmanager
+def _recording(graph, **kw):
+    """``torch.cuda.graph(graph)`` with no garbage collection while the stream records (as graphed.py): a collection
+    that fires in the middle of a capture finalises whatever died in earlier cycles -- graphs, events, library handles
+    -- and those are driver calls a capture does not allow (the process aborts).  ``torch.cuda.graph`` collects once
+    before the capture begins; that explicit collection runs as before."""
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if collecting:
+            gc.enable()
 
 
 class GraphedMMFSNet:
@@ -44,7 +63,7 @@ class GraphedMMFSNet:
                     net(self._sample, self._res, proj, self._mask, bank_repeat=bank_repeat)
             torch.cuda.current_stream(sample.device).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with _recording(self.graph):
                 self._out = net(self._sample, self._res, proj, self._mask, bank_repeat=bank_repeat)
             # The recorded kernels read the blocks' kept artefacts (folded weights, parameter-only tables, position
             # tables) at the addresses they had during the capture: hold them, so that an invalidation of the modules'
@@ -93,7 +112,7 @@ class GraphedLlamaMMFSStack:
                     self._run()
             torch.cuda.current_stream(hidden.device).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with _recording(self.graph):
                 self._out = self._run()
             # (as GraphedMMFSNet: what the recorded kernels read stays alive with the graph)
             self._pinned = [(l.attn._tables, l._gate_fold._kept, getattr(l, "_gate_tanh", None), l.attn.__dict__.get("_ratios_f32"))
@@ -141,7 +160,7 @@ class GraphedTrainingStep:
                 self._clear()
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with _recording(self.graph):
             self._out = self._run()
         self._in_grads = [x.grad for x in self._in]
         self._param_grads = [p.grad for p in self.params]      # (the buffers the recorded backward writes)

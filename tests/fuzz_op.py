@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mm-interleaved_amd"), os.path.join(ROOT, "tests")]
 import MultiScaleDeformableAttention as MSDA  # noqa: E402
 from oracle import msda_oracle  # noqa: E402
+from helpers import bound_ratios  # noqa: E402
 
 TOL = {torch.float64: 1e-12, torch.float32: 1e-5, torch.float16: 1e-3, torch.bfloat16: 8e-3}
 
@@ -142,7 +143,15 @@ def one_case(rng, idx):
         worst = max(worst, err / (TOL[dtype] * scale))
         if err > TOL[dtype] * scale:
             return f"FAIL {desc}: {name} err {err:.3e} > {TOL[dtype]:.0e} * {scale:.3g}"
-    return f"ok   {desc}  ({worst:.2f} of the bar)"
+    # and element by element (tests/helpers.py): finite entries only, equal finiteness, samples near a crossing left out
+    # of grad_loc, an element with nothing to add up exactly zero
+    x = dict(value=value, shapes=sh, start=st, loc=loc, attn=attn, grad=grad)
+    res = bound_ratios([out.double().cpu().numpy(), gv.double().cpu().numpy(), gl.double().cpu().numpy(),
+                        ga.double().cpu().numpy()], x, dtype)
+    for name, (ratio, where, err, bnd) in res.items():
+        if not ratio <= 1.0:
+            return f"FAIL {desc}: {name} {ratio:.3g} x its element's bound at {where} (err {err:.3e}, bound {bnd:.3e})"
+    return f"ok   {desc}  ({worst:.2f} of the bar; " + " ".join(f"{n} {r[0]:.2f}" for n, r in res.items()) + " of the bounds)"
 
 
 if __name__ == "__main__":

@@ -1317,6 +1317,28 @@ def test_mmfs_net_16bit_no_grad_at_512px_geometry_and_batch(dtype, bar):
 
 
 # ---------------------------------------------------------------- a training step as one HIP graph
+def test_graph_recordings_run_no_garbage_collection():
+    """A collection that fires while a stream records finalises whatever died earlier -- graphs, events -- and those
+    driver calls are not allowed inside a capture: the process aborts (seen in the checkpointed SD step below, where
+    the checkpoint's hooks allocate enough to trigger one).  The recordings of mmfs_amd.graphs keep the collector off
+    for the capture and hand it back on afterwards."""
+    import gc
+    from mmfs_amd.graphs import GraphedTrainingStep
+    w = torch.ones(64, device=DEV, requires_grad=True)
+    seen = []
+
+    def fn(x):
+        if torch.cuda.is_current_stream_capturing():
+            seen.append(gc.isenabled())
+        return (x * w,)
+    x = torch.rand(64, device=DEV, requires_grad=True)
+    assert gc.isenabled()
+    step = GraphedTrainingStep(fn, [x], [torch.ones(64, device=DEV)], [w])
+    assert seen == [False] and gc.isenabled()
+    outs, gin = step([x.detach() * 2], [torch.ones(64, device=DEV)])
+    assert torch.equal(outs[0], x.detach() * 2) and torch.equal(gin[0], torch.ones(64, device=DEV))
+
+
 @pytest.mark.parametrize("dtype, tol", [(torch.float32, 1e-5), (torch.bfloat16, 0.0)], ids=["f32", "bf16"])
 def test_graphed_training_step_replays_the_eager_step(dtype, tol):
     """mmfs_amd.graphs.GraphedTrainingStep: forward + backward of the toy MMFSNet (training mode, gradient checkpointing on

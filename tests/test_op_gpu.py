@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, level_tables, load_golden, make_inputs, max_abs
+from helpers import GOLDEN, assert_within_bounds, level_tables, load_golden, make_inputs, max_abs
 from oracle import msda_oracle
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +50,9 @@ def run_oracle(x):
     return out, gv, gl, ga
 
 
-def check(got, want, dtype, what=""):
+def check(got, want, x, dtype, what="", own_ref=False, gamma=None):
+    """The max-abs bars below, and the per-element bound of tests/helpers.py on all four outputs of inputs ``x``
+    (against the oracle on ``x``; against ``want`` with ``own_ref``, for tests that zero reference entries on purpose)."""
     tol = TOL[dtype]
     names = ("out", "grad_value", "grad_loc", "grad_attn")
     for n, g, w in zip(names, got, want):
@@ -66,6 +68,8 @@ def check(got, want, dtype, what=""):
             excess = np.abs(g64 - w64)[fin] - tol * (np.abs(w64)[fin] + 0.05 * scale)
             assert excess.size == 0 or float(excess.max()) <= 0.0, \
                 f"{what} {n}: an element is off by {float(excess.max()):.3e} more than {tol:.1e} * (|ref| + 0.05 * {scale:.3g})"
+    res = assert_within_bounds(got, x, dtype, what, want=want if own_ref else None, gamma=gamma)
+    print(f"BOUND {str(dtype)[6:]} {what}: " + " ".join(f"{n}={r[0]:.3g}" for n, r in res.items()))
 
 
 def golden_inputs(z, dtype):
@@ -84,14 +88,14 @@ def test_hip_matches_reference_goldens(name, dtype):
     want = [z["out_f64"], z["grad_value_f64"], z["grad_loc_f64"], z["grad_attn_f64"]]
     if dtype == torch.float64 and z["grad_value_f64"].dtype == np.float32:
         want[1] = run_oracle(x)[1]            # golden stored in fp32: use the (pinned) oracle
-    check(got, want, dtype, name)
+    check(got, want, x, dtype, name)
 
 
 @pytest.mark.parametrize("name", ["op_g1_d64", "op_g3_llm_n1", "op_g3_rect_n3", "op_g3_sd_n4"])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_hip_16bit_against_oracle_on_rounded_goldens(name, dtype):
     x = golden_inputs(load_golden(name), dtype)
-    check(run_hip(x, dtype), run_oracle(x), dtype, name)
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, name)
 
 
 CASES = [
@@ -113,7 +117,7 @@ CASES = [
 def test_hip_matches_oracle_seeded(case, dtype):
     B, H, D, Nq, P, shapes = case
     x = make_inputs(B, H, D, Nq, P, shapes, seed=7, loc_range=(-0.15, 1.15), dtype=dtype)
-    check(run_hip(x, dtype), run_oracle(x), dtype, str(case[:5]))
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, str(case[:5]))
 
 
 HYBRID_CASES = [
@@ -144,7 +148,7 @@ def test_hybrid_dense_levels_match_oracle(case, dtype, monkeypatch):
     monkeypatch.setattr(MSDA, "_event_log", None)
     names = {n for n, _, _ in log}
     assert "msda_bwd_taps_coarse" in names, names
-    check(got, run_oracle(x), dtype, f"hybrid {case[:5]}")
+    check(got, run_oracle(x), x, dtype, f"hybrid {case[:5]}")
 
 
 @pytest.mark.parametrize("algo", ["tile", "block", "pixel"])
@@ -162,7 +166,7 @@ def test_grad_value_generations_agree_with_oracle(algo, dtype, monkeypatch):
                     loc_range=(-0.3, 1.3), dtype=dtype)
     x["loc"][:, :40, :, 3] = x["loc"][:, :40, :, 3] * 0.05 + 0.5       # hot spot: long lists on a few blocks
     x["loc"] = x["loc"].to(dtype).to(torch.float64)                    # oracle and device see the same numbers
-    check(run_hip(x, dtype), run_oracle(x), dtype, f"value algo {algo}")
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, f"value algo {algo}")
 
 
 SORT_ROUTES = {
@@ -197,7 +201,7 @@ def test_cell_sort_routes_match_oracle(route, monkeypatch):
     x = make_inputs(4, 8, 32, Nq, P, [(32, 16), (16, 8), (8, 4), (4, 2)], seed=31, loc_range=(-0.1, 1.1), dtype=dtype)
     x["attn"][:, ::7, :, 1] = 0.0                               # zero weights leave no record
     try:
-        check(run_hip(x, dtype), run_oracle(x), dtype, f"sort route {route}")
+        check(run_hip(x, dtype), run_oracle(x), x, dtype, f"sort route {route}")
     finally:
         MSDA._ws_cache.clear()
 
@@ -218,7 +222,7 @@ def test_cell_sort_of_many_small_slices(dtype, P, Nq, hot, variant, monkeypatch)
     if hot:                                                     # every sample of a level in a few cells: long lists, cut items
         x["loc"][:, :, :, 1] = (x["loc"][:, :, :, 1] * 0.05 + 0.5).to(dtype).to(torch.float64)
     try:
-        check(run_hip(x, dtype), run_oracle(x), dtype, f"small slices, {variant}")
+        check(run_hip(x, dtype), run_oracle(x), x, dtype, f"small slices, {variant}")
     finally:
         MSDA._ws_cache.clear()
 
@@ -230,13 +234,13 @@ def test_every_query_on_one_spot_overflows_the_block_lists(dtype):
     chip and added into accumulator slots (msda_bwd_block_overflow / _ovf_store)."""
     x = make_inputs(1, 2, 64, 1500, 4, [(8, 8), (4, 4)], seed=5, dtype=dtype)
     x["loc"] = (x["loc"] * 0.04 + 0.48).to(dtype).to(torch.float64)     # all 6000 samples of a level in ~1 cell
-    check(run_hip(x, dtype), run_oracle(x), dtype, "hot spot overflow")
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, "hot spot overflow")
 
 
 def test_many_levels_fall_back_to_pixel_stationary():
     """L = 130 > the block reduce's level table: the pixel-stationary kernels take over."""
     x = make_inputs(1, 2, 32, 12, 2, [(3, 2)] * 130, seed=4, dtype=torch.bfloat16)
-    check(run_hip(x, torch.bfloat16), run_oracle(x), torch.bfloat16, "L=130")
+    check(run_hip(x, torch.bfloat16), run_oracle(x), x, torch.bfloat16, "L=130")
 
 
 @pytest.mark.parametrize("n_levels", [33, 40, 72, 128])
@@ -247,7 +251,7 @@ def test_level_rows_beyond_the_cached_ones(n_levels, dtype):
     different sizes so that a wrong row shows."""
     shapes = [((3, 2), (5, 4), (2, 7), (6, 6))[i % 4] for i in range(n_levels)]
     x = make_inputs(1, 2, 32, 40, 2, shapes, seed=6, dtype=dtype)
-    check(run_hip(x, dtype), run_oracle(x), dtype, f"L={n_levels}")
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, f"L={n_levels}")
 
 
 def test_hybrid_off_uses_plain_kernels(monkeypatch):
@@ -259,7 +263,7 @@ def test_hybrid_off_uses_plain_kernels(monkeypatch):
     got = run_hip(x, torch.bfloat16, use_autograd=False)
     monkeypatch.setattr(MSDA, "_event_log", None)
     assert not any("coarse" in n for n, _, _ in log)
-    check(got, run_oracle(x), torch.bfloat16, "hybrid off")
+    check(got, run_oracle(x), x, torch.bfloat16, "hybrid off")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -270,7 +274,7 @@ def test_atomic_backward_path_matches_oracle(case, dtype, monkeypatch):
     monkeypatch.setattr(MSDA, "_bwd_algo", "atomic")
     B, H, D, Nq, P, shapes = case
     x = make_inputs(B, H, D, Nq, P, shapes, seed=9, loc_range=(-0.15, 1.15), dtype=dtype)
-    check(run_hip(x, dtype), run_oracle(x), dtype, "atomic " + str(case[:5]))
+    check(run_hip(x, dtype), run_oracle(x), x, dtype, "atomic " + str(case[:5]))
 
 
 def test_non_canonical_level_table_falls_back_and_is_right():
@@ -286,7 +290,7 @@ def test_non_canonical_level_table_falls_back_and_is_right():
              loc=rt(torch.rand(B, Nq, H, 2, P, 2, generator=g) * 1.2 - 0.1),
              attn=rt(torch.rand(B, Nq, H, 2, P, generator=g)), grad=rt(torch.randn(B, Nq, H * D, generator=g)))
     got, want = run_hip(x, torch.float32), run_oracle(x)
-    check(got, want, torch.float32, "gapped levels")
+    check(got, want, x, torch.float32, "gapped levels")
     assert not got[1][:, 9:12].any() and not got[1][:, 36:].any()      # untouched rows are zero
 
 
@@ -317,7 +321,7 @@ def test_fresh_level_tensors_cost_no_host_sync(dtype):
             torch.cuda.set_sync_debug_mode("default")
         res = [out.detach(), vv.grad, ll.grad, aa.grad]
     torch.cuda.synchronize()
-    check([r.double().cpu().numpy() for r in res], run_oracle(x), dtype, "fresh level tensors")
+    check([r.double().cpu().numpy() for r in res], run_oracle(x), x, dtype, "fresh level tensors")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
@@ -334,7 +338,7 @@ def test_unverified_gapped_table_is_served_by_the_sorted_backward(dtype):
              loc=rt(torch.rand(B, Nq, H, 3, P, 2, generator=g) * 1.2 - 0.1),
              attn=rt(torch.rand(B, Nq, H, 3, P, generator=g)), grad=rt(torch.randn(B, Nq, H * D, generator=g)))
     got, want = run_hip(x, dtype), run_oracle(x)
-    check(got, want, dtype, "gapped, unverified levels")
+    check(got, want, x, dtype, "gapped, unverified levels")
     owned = np.zeros(S, bool)
     for (h, w), s0 in zip(shapes.tolist(), start.tolist()):
         owned[s0:s0 + h * w] = True
@@ -360,7 +364,7 @@ def test_more_than_65536_queries_leave_the_compact_records():
     """The matrix-core reduce keeps the query index in 16 bits of its 8-byte records; with more queries the
     2x2-block reduce (16-byte records) takes over for 16-bit storage too."""
     x = make_inputs(1, 1, 32, 66000, 4, [(6, 5), (3, 4)], seed=12, dtype=torch.bfloat16)
-    check(run_hip(x, torch.bfloat16), run_oracle(x), torch.bfloat16, "Nq = 66000")
+    check(run_hip(x, torch.bfloat16), run_oracle(x), x, torch.bfloat16, "Nq = 66000")
 
 
 def test_skewed_locations_overflow_the_tile_lists():
@@ -370,10 +374,10 @@ def test_skewed_locations_overflow_the_tile_lists():
     shapes = [(8, 8), (4, 4)]
     x = make_inputs(B, H, D, Nq, P, shapes, seed=13, dtype=torch.bfloat16)
     x["loc"] = (x["loc"] * 0.02 + 0.40).to(torch.bfloat16).double()    # tight cluster
-    check(run_hip(x, torch.bfloat16), run_oracle(x), torch.bfloat16, "skew")
+    check(run_hip(x, torch.bfloat16), run_oracle(x), x, torch.bfloat16, "skew")
     x32 = make_inputs(B, H, 32, Nq, P, shapes, seed=14, dtype=torch.float32)
     x32["loc"] = x32["loc"] * 0.0 + 0.3                                 # exactly one spot
-    check(run_hip(x32, torch.float32), run_oracle(x32), torch.float32, "skew32")
+    check(run_hip(x32, torch.float32), run_oracle(x32), x32, torch.float32, "skew32")
 
 
 def test_direct_extension_calls_match_autograd_path():
@@ -381,7 +385,7 @@ def test_direct_extension_calls_match_autograd_path():
     a = run_hip(x, torch.float32, use_autograd=True)
     b = run_hip(x, torch.float32, use_autograd=False)
     assert max_abs(a[0], b[0]) == 0.0                      # forward is deterministic
-    check(b, run_oracle(x), torch.float32)
+    check(b, run_oracle(x), x, torch.float32, "direct calls")
 
 
 def test_edge_locations_follow_the_kernel_not_grid_sample():
@@ -396,7 +400,7 @@ def test_edge_locations_follow_the_kernel_not_grid_sample():
     for dtype in (torch.float64, torch.float32):
         got, want = run_hip(x, dtype), run_oracle(x)
         assert np.isfinite(got[0]).all() and np.isfinite(got[2]).all()
-        check(got, want, dtype, "edges")
+        check(got, want, x, dtype, "edges")
 
 
 def test_non_finite_values_outside_the_tap_do_not_leak():
@@ -531,7 +535,7 @@ def test_zero_attention_samples_are_skipped_not_miscounted(dtype):
     x["attn"] = (x["attn"] * keep).to(dtype).to(torch.float64)
     got = run_hip(x, dtype, use_autograd=False)
     want = run_oracle(x)
-    check(got, want, dtype, "zero attention")
+    check(got, want, x, dtype, "zero attention")
     assert np.abs(want[3][keep.expand_as(x["attn"]).numpy() == 0]).max() > 1e-3     # the case is not vacuous
     assert np.abs(got[0][1, :150]).max() == 0.0
 
@@ -818,7 +822,7 @@ def test_query_wave_forward_is_the_default_for_long_runs(monkeypatch):
     a, g = run_fwd(x, torch.bfloat16, "auto"), run_fwd(x, torch.bfloat16, "waves")
     assert max_abs(a, g) == 0.0
     assert max_abs(a, run_fwd(x, torch.bfloat16, "gather")) > 0.0        # (a different summation order: not bit-equal)
-    check(run_hip(x, torch.bfloat16), run_oracle(x), torch.bfloat16, "auto-routed")
+    check(run_hip(x, torch.bfloat16), run_oracle(x), x, torch.bfloat16, "auto-routed")
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -863,7 +867,7 @@ def test_unverified_overlapping_table_is_served_by_the_atomic_fallback(dtype):
     assert len(said) == 1 and said[0].category is RuntimeWarning            # ... and the shim says so, once
     # an ordinary fresh table right after it, through the same (recycled) workspace: the fallback stays out of the way
     x2 = make_inputs(2, 4, 64, 50, 4, [(12, 9), (6, 5), (3, 3)], seed=31, dtype=dtype)
-    check(run_hip(x2, dtype), run_oracle(x2), dtype, "after a refused table")
+    check(run_hip(x2, dtype), run_oracle(x2), x2, dtype, "after a refused table")
     assert MSDA.check_level_table_status(synchronize=True) is False
     # out-of-range: level 1 points past the end of value -- the reference would write out of bounds; here the rows
     # that exist get their gradients, the others are skipped, nothing faults
@@ -873,7 +877,7 @@ def test_unverified_overlapping_table_is_served_by_the_atomic_fallback(dtype):
     assert bool(torch.isfinite(gv2.float()).all())
     assert MSDA.check_level_table_status(synchronize=True) is True
     # registered (the shim then knows it is not canonical): the float-atomic path serves it directly
-    check(run_hip(x, dtype, use_autograd=False, register=True), want, dtype, "overlapping, registered")
+    check(run_hip(x, dtype, use_autograd=False, register=True), want, x, dtype, "overlapping, registered")
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -903,11 +907,11 @@ def test_many_points_per_level(case, dtype, route, monkeypatch):
         monkeypatch.setattr(MSDA, "_bwd_algo", "atomic")
     got = run_hip(x, dtype, use_autograd=False, register=(route == "registered"))
     want = run_oracle(x)
-    check(got, want, dtype, f"P={P} {route}")
+    check(got, want, x, dtype, f"P={P} {route}")
     if route == "registered":
         # many vectors per query: the kept scan takes them as groups of virtual queries (default) -- or the scalar scan does
         monkeypatch.setenv("MMFS_SORT_MANY_POINTS", "0")
-        check(run_hip(x, dtype, use_autograd=False, register=True), want, dtype, f"P={P} scalar scan")
+        check(run_hip(x, dtype, use_autograd=False, register=True), want, x, dtype, f"P={P} scalar scan")
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -958,7 +962,7 @@ def test_lds_levels_taps_match_oracle(case, dtype, route, monkeypatch):
     got = run_hip(x, dtype, use_autograd=False, register=(route == "registered"))
     monkeypatch.setattr(MSDA, "_event_log", None)
     assert not any("coarse" in n for n, _, _ in log), [n for n, _, _ in log]         # one kernel does every level
-    check(got, run_oracle(x), dtype, f"taps lds {route} {case[:5]}")
+    check(got, run_oracle(x), x, dtype, f"taps lds {route} {case[:5]}")
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -977,7 +981,7 @@ def test_lds_levels_taps_are_the_default_and_agree_with_the_row_gather(dtype, mo
         assert max_abs(a, b) == 0.0                                                  # auto IS the fused kernel here
     want = run_oracle(x)
     for algo in ("lds", "gather"):
-        check(res[algo], want, dtype, algo)
+        check(res[algo], want, x, dtype, algo)
     # the lazy hint (MMFS's softmax never reads the gradients of a zero weight): zeros there, the rest bit-equal
     dev = lambda t: t.to(DEV, dtype) if t.is_floating_point() else t.to(DEV)
     args = [dev(x[k]) for k in ("value", "shapes", "start", "loc", "attn")] + [dev(x["grad"]).reshape(2, 352, -1), 1]
@@ -1018,7 +1022,7 @@ def test_staged_sort_and_reduce_on_a_foreign_workspace_do_nothing():
             assert rc == 0
         torch.cuda.synchronize()
         assert bool((gv == 7.0).all())                          # nothing was written
-    check(run_hip(x, torch.bfloat16, register=True), run_oracle(x), torch.bfloat16, "after staged calls on foreign workspaces")
+    check(run_hip(x, torch.bfloat16, register=True), run_oracle(x), x, torch.bfloat16, "after staged calls on foreign workspaces")
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -1033,14 +1037,14 @@ def test_value_plan_hosted_by_the_taps_kernel(dtype, monkeypatch):
     for setting in ("1", "0", "1"):
         monkeypatch.setenv("MMFS_PREPARE_IN_TAPS", setting)
         for _ in range(3):
-            check(run_hip(x, dtype, use_autograd=False, register=True), want, dtype, f"plan in taps = {setting}")
+            check(run_hip(x, dtype, use_autograd=False, register=True), want, x, dtype, f"plan in taps = {setting}")
     # heads of 64 channels: the dense-levels kernel (csrc/msda_dense.hip) is the host
     x = make_inputs(2, 4, 64, 300, 8, [(32, 32), (16, 16), (8, 8)] * 2, seed=41, loc_range=(-0.1, 1.1), dtype=dtype)
     want = run_oracle(x)
     for setting in ("1", "0", "1"):
         monkeypatch.setenv("MMFS_PREPARE_IN_TAPS", setting)
         for _ in range(2):
-            check(run_hip(x, dtype, use_autograd=False, register=True), want, dtype, f"plan in dense taps = {setting}")
+            check(run_hip(x, dtype, use_autograd=False, register=True), want, x, dtype, f"plan in dense taps = {setting}")
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -50,7 +50,7 @@ def test_sorted_backward_matches_oracle(case, dtype, sorted_route):
     x["loc"][0, 5, 1 % H, -1, 0, 1] = float("inf")
     got = run_hip(x, dtype, use_autograd=False, register=True)
     ran_sorted(sorted_route)
-    check(got, run_oracle(x), dtype, f"sorted {case[:5]}")
+    check(got, run_oracle(x), x, dtype, f"sorted {case[:5]}")
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -81,7 +81,7 @@ def test_sorted_backward_exact_pixel_centres_and_borders(dtype, sorted_route):
     gl_got, gl_want = got[2].copy(), np.asarray(want[2], dtype=np.float64).reshape(got[2].shape).copy()
     gl_got[near] = 0.0
     gl_want[near] = 0.0
-    check([got[0], got[1], gl_got, got[3]], [want[0], want[1], gl_want, want[3]], dtype, "centres")
+    check([got[0], got[1], gl_got, got[3]], [want[0], want[1], gl_want, want[3]], x, dtype, "centres", own_ref=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16])
@@ -106,7 +106,7 @@ def test_sorted_backward_lazy_zero_attn(dtype, sorted_route):
     w_ga[zero] = 0.0
     got = [np.asarray(want[0]), gv.double().cpu().numpy(), gl.double().cpu().numpy(), ga.double().cpu().numpy()]
     assert np.all(got[3][zero] == 0.0) and np.all(got[2][zero] == 0.0)
-    check(got, [want[0], want[1], w_gl, w_ga], dtype, "lazy")
+    check(got, [want[0], want[1], w_gl, w_ga], x, dtype, "lazy", own_ref=True)
 
 
 def test_sorted_backward_non_finite_value_rows_stay_with_their_samples(sorted_route):
