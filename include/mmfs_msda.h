@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14: + mmfs_msda_forward_shared, mmfs_sample_forward_heads_shared: one value bank of Bv rows serves
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_bank_quantize_fp8, mmfs_msda_forward_fp8, mmfs_sample_forward_heads_fp8:
+                                   *     the inference-only fp8 (e4m3) value bank with fp32 scales, see "fp8 bank" below
+                                   * 14: + mmfs_msda_forward_shared, mmfs_sample_forward_heads_shared: one value bank of Bv rows serves
                                    *     B = g * Bv query rows (MMFS_BANK_TILE / MMFS_BANK_INTERLEAVE) without being copied
                                    * 13: + mmfs_msda_backward_sorted (+ _workspace_bytes): the whole backward on the cell-sorted records -- grad_loc / grad_attn
                                    *     from the records the grad_value sort makes (csrc/msda_bwd_taps_sorted.hip), no per-sample value-row gather;
@@ -506,6 +508,40 @@ int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t
                                      void *out, float *sink,
                                      int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
                                      int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream);
+
+/*
+ * fp8 bank (inference only).  A value bank read many times over (a generation's kept projections) may be stored at 8 bits:
+ * ``q`` [Bv, S, H, D] OCP e4m3 (e4m3fn: bias 7, max 448, 0x7f / 0xff NaN, no infinities -- NOT the fnuz format) and
+ * ``scale`` [Bv, H*D] fp32, one per (bank row, channel); element (b, s, h, d) stands for  float(q) * scale[b, h*D + d].
+ * The kernels sum  w * float(q)  in fp32 and multiply by the scale once per output channel at the store.
+ *
+ * mmfs_bank_quantize_fp8: x [nbanks, Bv, R, C] of ``dtype`` (MMFS_F32 / MMFS_F16 / MMFS_BF16; R = rows per bank row, n*S;
+ * C = H*D, a multiple of 16) -> q [nbanks, Bv, R, C] e4m3, scale [nbanks, Bv, C] fp32.  nbanks independent banks, one call.
+ *     amax[b, c] = max |x| over the FINITE elements of bank row b, column c;   scale = amax / 448  (fp32 division)
+ *     q = e4m3(RNE(clamp(x / scale, -448, 448)));   scale == 0 -> q = 0 (+0);   x not finite -> q = 0x7f (NaN)
+ * Deterministic (the column maxima are order-independent).  x, q and scale 16-byte aligned.
+ *
+ * mmfs_msda_forward_fp8: mmfs_msda_forward_shared on an fp8 bank (pass Bv = B, MMFS_BANK_TILE for an unshared one); ``dtype``
+ * is the type of loc / attn / out (MMFS_F32 / MMFS_F16 / MMFS_BF16).  The row gather only.  D = 16 * 2^k, k <= 4, else
+ * MMFS_E_UNSUPPORTED (dequantise and use the 16-bit entries).
+ * mmfs_sample_forward_heads_fp8: mmfs_sample_forward_heads_shared on an fp8 bank plus its ``scale``; the ignore-token term
+ * and its roundings stay in ``dtype``.  The same D rule.  For the lane groups it uses (mmfs_sample_forward_groups), ask
+ * with MMFS_BF16 and D / 2: 16 channels per lane, the lanes of a bf16 bank of half the width.
+ * Argument errors come back before any launch, as for the shared entries.
+ */
+int mmfs_bank_quantize_fp8(int dtype, const void *x, int64_t nbanks, int64_t Bv, int64_t R, int64_t C,
+                           void *q, float *scale, void *stream);
+int mmfs_msda_forward_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                          const void *loc, const void *attn, void *out,
+                          int64_t B, int64_t Bv, int layout, int64_t S, int64_t H, int64_t D,
+                          int64_t L, int64_t Nq, int64_t P, void *stream);
+int mmfs_sample_forward_heads_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                                  const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                                  const void *off_tab, const void *att_tab,
+                                  const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                                  void *out, float *sink,
+                                  int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                                  int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream);
 
 /* How many lane groups share ONE query's samples in mmfs_sample_forward* for this shape (``nL`` = n * L level rows):
  * 1 = the samples are summed in their order, ``out`` bit-identical to mmfs_plan_forward + mmfs_msda_forward;

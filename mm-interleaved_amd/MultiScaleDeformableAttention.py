@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 __all__ = ["ms_deform_attn_forward", "ms_deform_attn_backward", "register_level_tables", "library_path",
-           "build_info", "check_level_table_status", "value_row_map"]
+           "build_info", "check_level_table_status", "value_row_map", "quantize_bank_fp8", "quantize_bank_fp8_reference",
+           "dequantize_bank_fp8", "FP8_BANK_DTYPE"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("MMFS_MSDA_LIB", os.path.join(_HERE, "libmmfs_msda.so"))
@@ -55,6 +56,10 @@ _lib.mmfs_msda_forward_flags.restype = _int
 _lib.mmfs_msda_forward_flags.argtypes = [_int] + [_vp] * 6 + [_i64] * 7 + [ctypes.c_uint, _vp]
 _lib.mmfs_msda_forward_shared.restype = _int
 _lib.mmfs_msda_forward_shared.argtypes = [_int] + [_vp] * 6 + [_i64] * 2 + [_int] + [_i64] * 6 + [ctypes.c_uint, _vp]
+_lib.mmfs_bank_quantize_fp8.restype = _int
+_lib.mmfs_bank_quantize_fp8.argtypes = [_int, _vp] + [_i64] * 4 + [_vp, _vp, _vp]
+_lib.mmfs_msda_forward_fp8.restype = _int
+_lib.mmfs_msda_forward_fp8.argtypes = [_int] + [_vp] * 7 + [_i64] * 2 + [_int] + [_i64] * 6 + [_vp]
 _lib.mmfs_msda_backward.restype = _int
 _lib.mmfs_msda_backward.argtypes = [_int] + [_vp] * 10 + [_i64] * 8 + [ctypes.c_uint, _vp]
 _lib.mmfs_msda_backward_checked.restype = _int
@@ -308,19 +313,124 @@ def check_level_table_status(device=None, synchronize=False):
     return seen
 
 
+# ---- the inference-only fp8 value bank (include/mmfs_msda.h "fp8 bank"): q [Bv, S, H, D] OCP e4m3
+# (torch.float8_e4m3fn -- not the fnuz format) with one fp32 scale per (bank row, channel), scale [Bv, H*D]; element
+# (b, s, h, d) stands for float(q) * scale[b, h*D + d].
+FP8_BANK_DTYPE = torch.float8_e4m3fn
+_FP8_MAX = 448.0
+_FP8_NAN = 0x7f
+
+
+def _bank_dims(x):
+    _require(x.dim() in (4, 5), f"a bank is [Bv, S, H, D] or a batch of banks [K, Bv, S, H, D], not {tuple(x.shape)}")
+    S, H, D = x.shape[-3:]
+    return tuple(x.shape[:-3]), int(S), int(H) * int(D)
+
+
+def quantize_bank_fp8_reference(x):
+    """The quantiser's rule as torch operations (the CPU path, and what the kernel is tested against bit for bit):
+    x [Bv, S, H, D] (or [K, Bv, S, H, D]) -> (q e4m3 of x's shape, scale fp32 [Bv, H*D] (or [K, Bv, H*D])).
+        amax = max |x| over the FINITE elements of a (bank row, channel) column;  scale = amax / 448 (fp32 division);
+        q = e4m3(RNE(clamp(x / scale, -448, 448)));  scale == 0 -> +0;  a non-finite x -> the NaN code 0x7f, unclamped."""
+    lead, S, C = _bank_dims(x)
+    xr = x.float().reshape(*lead, S, C)
+    finite = torch.isfinite(xr)
+    if S > 0:
+        amax = torch.where(finite, xr.abs(), torch.zeros((), device=xr.device)).amax(dim=-2)
+    else:
+        amax = torch.zeros(*lead, C, device=xr.device)
+    scale = amax / _FP8_MAX
+    s = scale.unsqueeze(-2)
+    y = torch.where(s != 0, (xr / torch.where(s != 0, s, torch.ones((), device=xr.device))).clamp(-_FP8_MAX, _FP8_MAX),
+                    torch.zeros((), device=xr.device))
+    qb = y.to(FP8_BANK_DTYPE).view(torch.uint8)
+    qb = torch.where(finite, qb, torch.full((), _FP8_NAN, dtype=torch.uint8, device=xr.device))
+    return qb.view(FP8_BANK_DTYPE).reshape(x.shape), scale.contiguous()
+
+
+def quantize_bank_fp8(x):
+    """x [Bv, S, H, D] or a batch of K banks [K, Bv, S, H, D] (f32 / f16 / bf16) -> (q, scale) by the rule of
+    ``quantize_bank_fp8_reference``: on the GPU the kernel (csrc/mmfs_bank_fp8.hip, every bank in one call, bit-identical
+    to the rule), on the CPU the rule itself.  Inference only: nothing here is differentiable."""
+    lead, S, C = _bank_dims(x)
+    if not x.is_cuda:
+        return quantize_bank_fp8_reference(x)
+    _require(x.dtype in (torch.float32, torch.float16, torch.bfloat16), f"quantize_bank_fp8: unsupported dtype {x.dtype}")
+    x = _aligned(x.contiguous())
+    q = torch.empty(x.shape, dtype=FP8_BANK_DTYPE, device=x.device)
+    scale = torch.empty(*lead, C, dtype=torch.float32, device=x.device)
+    K = lead[0] if len(lead) == 2 else 1
+    Bv = lead[-1]
+    with _on_device(x.device):
+        status = _launch("bank_quantize_fp8", x.device, _lib.mmfs_bank_quantize_fp8, _DTYPE_CODE[x.dtype], x.data_ptr(),
+                         K, Bv, S, C, q.data_ptr(), scale.data_ptr(), _stream(x.device))
+    if status == _E_UNSUPPORTED:                     # (H*D not a multiple of 16: the rule, on the device)
+        return quantize_bank_fp8_reference(x)
+    _check(status, "quantize_bank_fp8")
+    return q, scale
+
+
+def dequantize_bank_fp8(q, scale, dtype=torch.float32):
+    """float(q) * scale as ``dtype`` -- the bank an fp8 bank stands for."""
+    lead, S, C = _bank_dims(q)
+    return (q.float().reshape(*lead, S, C) * scale.float().unsqueeze(-2)).to(dtype).reshape(q.shape)
+
+
+def _forward_fp8(value, value_scale, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
+                 value_repeat):
+    """ms_deform_attn_forward on an fp8 bank: the output has attn_weight's type."""
+    _validate([("value_scale", value_scale)], value)
+    if value_repeat is None:
+        B, S, H, D, L, Nq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+        Bv, layout = B, _VALUE_REPEAT["tile"]
+    else:
+        B, S, H, D, L, Nq, P, Bv = _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                value_repeat)
+        layout = _VALUE_REPEAT[value_repeat]
+    step = min(B, int(im2col_step)) if B > 0 else 1
+    _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
+    dt = attn_weight.dtype
+    _require(dt in (torch.float32, torch.float16, torch.bfloat16), f"fp8 bank: unsupported output dtype {dt}")
+    _require(value_scale.dtype == torch.float32 and tuple(value_scale.shape) == (value.shape[0], H * D),
+             f"value_scale must be fp32 [{value.shape[0]}, {H * D}], not {value_scale.dtype} {tuple(value_scale.shape)}")
+    if sampling_loc.dtype != dt:
+        sampling_loc = sampling_loc.to(dt)
+    value, value_scale = _aligned(value), _aligned(value_scale)
+    out = torch.empty((B, Nq, H * D), dtype=dt, device=value.device)
+    with _on_device(value.device):
+        status = _launch(
+            "msda_fwd", value.device, _lib.mmfs_msda_forward_fp8, _DTYPE_CODE[dt], value.data_ptr(), value_scale.data_ptr(),
+            spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+            out.data_ptr(), B, Bv, layout, S, H, D, L, Nq, P, _stream(value.device))
+    if status == _E_UNSUPPORTED:
+        # a head width the fp8 kernels do not serve (D not 16 * 2^k, k <= 4): the documented slow path -- the bank
+        # dequantised to the output type, then the ordinary forward
+        return ms_deform_attn_forward(dequantize_bank_fp8(value, value_scale, dt), spatial_shapes, level_start_index,
+                                      sampling_loc, attn_weight, im2col_step, value_repeat=value_repeat)
+    _check(status, "ms_deform_attn_forward")
+    return out
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                           im2col_step, *, value_repeat=None):
+                           im2col_step, *, value_repeat=None, value_scale=None):
     """Reference: ms_deform_attn_cuda_forward, src/cuda/ms_deform_attn_cuda.cu:21-81.
     ``value_repeat`` (an addition): None, or "tile" / "interleave" when ``value`` [Bv, S, H, D] is a bank shared by the
     B = g * Bv query rows of ``sampling_loc`` -- query row b reads bank row b % Bv ("tile", the order of
     ``torch.cat([value] * g)``) or b // g ("interleave", of ``value.repeat_interleave(g, 0)``).  The result is the op on
-    the expanded bank, bit for bit; the copy is never made (mmfs_msda_forward_shared)."""
+    the expanded bank, bit for bit; the copy is never made (mmfs_msda_forward_shared).
+    ``value_scale`` (an addition too): with ``value`` an fp8 bank (``FP8_BANK_DTYPE``, from ``quantize_bank_fp8``), its fp32
+    scales [Bv, H*D]; the output then has ``attn_weight``'s type (mmfs_msda_forward_fp8).  Forward only."""
     _require(isinstance(value, torch.Tensor) and value.is_cuda, "Not implemented on the CPU")
     if _status_words:
         check_level_table_status()
     _validate([("value", value), ("spatial_shapes", spatial_shapes),
                ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                ("attn_weight", attn_weight)], value)
+    if value.dtype == FP8_BANK_DTYPE or value_scale is not None:
+        _require(value.dtype == FP8_BANK_DTYPE and value_scale is not None,
+                 "an fp8 bank (torch.float8_e4m3fn) comes with its value_scale, and value_scale with an fp8 bank")
+        return _forward_fp8(value, value_scale, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
+                            value_repeat)
     if value_repeat is None:
         B, S, H, D, L, Nq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     else:

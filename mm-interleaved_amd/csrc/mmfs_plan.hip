@@ -300,16 +300,18 @@ __device__ __forceinline__ float rgroup_add(float v, int G)
     return v;
 }
 
-template <typename T, int LPI, int P>
+// BT: the bank's type, T or fp8e4m3_t (scales [Bv, H*D] applied at the store, as msda_fwd_vec; the ignore-token term
+// stays in T)
+template <typename T, int LPI, int P, typename BT>
 __global__ void __launch_bounds__(kThreads)
-mmfs_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ start,
+mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ start,
                 const T *__restrict__ off_q, const T *__restrict__ att_q,
                 const T *__restrict__ off_tab, const T *__restrict__ att_tab,
                 const int64_t *__restrict__ relpos, const float *__restrict__ ref, const float *__restrict__ ratios,
                 T *__restrict__ out, float *__restrict__ sink, const Dims d, const PlanDims pd, const int G,
-                const T *__restrict__ token)
+                const T *__restrict__ token, const float *__restrict__ vscale)
 {
-    typedef Vec16<T> V;
+    typedef Vec16<BT> V;
     constexpr int VEC = V::N;
     constexpr int QPB = kThreads / LPI;
     constexpr int KC = (kSampleRecs / QPB) > P ? (kSampleRecs / QPB) : P;      // samples per query per chunk: whole rows of P
@@ -331,10 +333,10 @@ mmfs_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const bool q_ok = q < d.Nq;
     const int nL = d.L;                                   // = n * levels per image
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;
-    const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
+    const BT *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;
+    const uint32_t row_bytes = (uint32_t)(HD * sizeof(BT));
     const uint32_t lane_off = (uint32_t)(lig * 16);
-    const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)bc.h * d.D) * (int64_t)sizeof(T));
+    const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)bc.h * d.D) * (int64_t)sizeof(BT));
     levels.load(shapes, start, nL, tid, kThreads);
     if (kPipe && tid < kThreads / 64) live[tid] = 0ull;
     const float sink_logit = -logf((float)nL);
@@ -534,12 +536,13 @@ mmfs_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     }
     if (q_ok) {
         T *o = out + (((int64_t)bc.b * d.Nq + q) * d.H + bc.h) * d.D + lig * VEC;
+        apply_scale<BT, VEC>(acc, vscale, (int64_t)value_row(d, bc.b) * HD + (int64_t)bc.h * d.D + lig * VEC);
         if (token != nullptr) {
             // the sinks' share goes to the ignore token (mmfs.py:236-241, 274): out + token * sink, with the framework
             // statement's roundings -- sampled output, sink weight and product each rounded to the storage type first
             const float sw = to_f32((T)ssum[qi]);
             float tk[VEC];
-            V::unpack(*reinterpret_cast<const uint4 *>(token + (int64_t)bc.h * d.D + lig * VEC), tk);
+            load_vec<T, VEC>(token + (int64_t)bc.h * d.D + lig * VEC, tk);
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
                 // (two roundings, as the framework's two kernels: the product must not be contracted into the sum --
@@ -549,7 +552,7 @@ mmfs_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                 acc[i] = to_f32((T)acc[i]) + to_f32((T)prod);
             }
         }
-        *reinterpret_cast<uint4 *>(o) = V::pack(acc);
+        store_vec<T, VEC, false>(o, acc);
     }
 }
 
@@ -571,16 +574,16 @@ constexpr int kDecodeMaxQ = 8;          // queries per (sample, head) up to whic
 constexpr int kDecodeMaxK = 256;        // samples per query held as tap records
 constexpr int kDecodeBatch = 4;         // samples in flight per lane group (16 row loads per lane)
 
-template <typename T, int LPI, int P>
+template <typename T, int LPI, int P, typename BT>
 __global__ void __launch_bounds__(64)
-mmfs_sample_decode(const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ start,
+mmfs_sample_decode(const BT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ start,
                    const T *__restrict__ off_q, const T *__restrict__ att_q,
                    const T *__restrict__ off_tab, const T *__restrict__ att_tab,
                    const int64_t *__restrict__ relpos, const float *__restrict__ ref, const float *__restrict__ ratios,
                    T *__restrict__ out, float *__restrict__ sink, const Dims d, const PlanDims pd, const int G,
-                   const T *__restrict__ token)
+                   const T *__restrict__ token, const float *__restrict__ vscale)
 {
-    typedef Vec16<T> V;
+    typedef Vec16<BT> V;
     constexpr int VEC = V::N;
     constexpr int NSUB = 64 / LPI;
     __shared__ float4 plan[kDecodeMaxK];                  // {x, y, weight} per sample, rounded to the storage type
@@ -591,9 +594,9 @@ mmfs_sample_decode(const T *__restrict__ value, const int64_t *__restrict__ shap
     const int q = (blockIdx.x / d.H) % d.Nq, b = blockIdx.x / d.H / d.Nq;
     const int nL = d.L;
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
-    const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
-    const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(T));
+    const BT *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
+    const uint32_t row_bytes = (uint32_t)(HD * sizeof(BT));
+    const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(BT));
     const float sink_logit = -logf((float)nL);
     const int64_t tk = (int64_t)b * pd.Lq + q;
 
@@ -701,11 +704,12 @@ mmfs_sample_decode(const T *__restrict__ value, const int64_t *__restrict__ shap
         for (int i = 0; i < VEC; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
     if (sub == 0) {
         T *o = out + (((int64_t)b * d.Nq + q) * d.H + h) * d.D + lig * VEC;
+        apply_scale<BT, VEC>(acc, vscale, (int64_t)value_row(d, b) * HD + (int64_t)h * d.D + lig * VEC);
         if (token != nullptr) {
             // (mmfs_sample_fwd's statement of the ignore-token term: sampled output, sink weight and product each rounded first)
             const float sw = to_f32((T)sink_sum);
             float tkn[VEC];
-            V::unpack(*reinterpret_cast<const uint4 *>(token + (int64_t)h * d.D + lig * VEC), tkn);
+            load_vec<T, VEC>(token + (int64_t)h * d.D + lig * VEC, tkn);
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
                 float prod = tkn[i] * sw;
@@ -713,7 +717,7 @@ mmfs_sample_decode(const T *__restrict__ value, const int64_t *__restrict__ shap
                 acc[i] = to_f32((T)acc[i]) + to_f32((T)prod);
             }
         }
-        *reinterpret_cast<uint4 *>(o) = V::pack(acc);
+        store_vec<T, VEC, false>(o, acc);
     }
 }
 
@@ -923,6 +927,14 @@ int mmfs_sample_forward_heads(int dtype, const void *value, const int64_t *shape
                                             n, M, Lr, Nr, stream);
 }
 
+static int sample_forward_any(int dtype, bool fp8, const void *value, const float *scale, const int64_t *shapes,
+                              const int64_t *start, const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                              const void *off_tab, const void *att_tab,
+                              const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                              void *out, float *sink,
+                              int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                              int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream);
+
 int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
                                      const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
                                      const void *off_tab, const void *att_tab,
@@ -931,9 +943,35 @@ int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t
                                      int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
                                      int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream)
 {
+    return sample_forward_any(dtype, false, value, nullptr, shapes, start, off_q, att_q, ld_off, ld_att, off_tab, att_tab, relpos,
+                              ref, ratios, token, out, sink, N, Nv, layout, S, Lq, H, D, L, P, n, M, Lr, Nr, stream);
+}
+
+int mmfs_sample_forward_heads_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                                  const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                                  const void *off_tab, const void *att_tab,
+                                  const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                                  void *out, float *sink,
+                                  int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                                  int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream)
+{
+    return sample_forward_any(dtype, true, q, scale, shapes, start, off_q, att_q, ld_off, ld_att, off_tab, att_tab, relpos,
+                              ref, ratios, token, out, sink, N, Nv, layout, S, Lq, H, D, L, P, n, M, Lr, Nr, stream);
+}
+
+// the shared-bank sampler on a 16-bit / fp32 bank of the output's type, or (fp8) on an e4m3 bank with its scales
+static int sample_forward_any(int dtype, bool fp8, const void *value, const float *scale, const int64_t *shapes,
+                              const int64_t *start, const void *off_q, const void *att_q, int64_t ld_off, int64_t ld_att,
+                              const void *off_tab, const void *att_tab,
+                              const int64_t *relpos, const float *ref, const float *ratios, const void *token,
+                              void *out, float *sink,
+                              int64_t N, int64_t Nv, int layout, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L,
+                              int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream)
+{
     using namespace mmfs;
     const int es = esize(dtype);
     if (!es) return MMFS_E_DTYPE;
+    const int bes = fp8 ? 1 : es;                                           // the bank's element size
     PlanDims pd;
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &pd);
     if (rc) return rc;
@@ -942,14 +980,15 @@ int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t
     if (S < 0 || D <= 0 || S > 0x7ffffffdLL || H * D > 0x7fffffffLL) return MMFS_E_DIMS;
     if (N * Lq * H == 0) return MMFS_OK;
     if (P == 16 || S == 0) return MMFS_E_UNSUPPORTED;                       // (P = 16: the two-kernel path)
-    const int vec = 16 / es;
+    const int vec = 16 / bes;
     if (D % vec) return MMFS_E_UNSUPPORTED;
     const int lpi = (int)(D / vec);
-    if (lpi < 1 || lpi > 64 || (lpi & (lpi - 1))) return MMFS_E_UNSUPPORTED;
-    if (S * H * D * (int64_t)es > kMaxSlabBytes) return MMFS_E_UNSUPPORTED;        // buffer-descriptor rows only
-    if (!value || !shapes || !start || !off_q || !att_q || !off_tab || !att_tab || !relpos || !ref || !ratios || !out)
+    if (lpi < 1 || lpi > (fp8 ? 16 : 64) || (lpi & (lpi - 1))) return MMFS_E_UNSUPPORTED;
+    if (S * H * D * (int64_t)bes > kMaxSlabBytes) return MMFS_E_UNSUPPORTED;       // buffer-descriptor rows only
+    if (!value || !shapes || !start || !off_q || !att_q || !off_tab || !att_tab || !relpos || !ref || !ratios || !out ||
+        (fp8 && !scale))
         return MMFS_E_NULLPTR;
-    if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)token) % 16) return MMFS_E_ALIGN;
+    if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)token | (uintptr_t)scale) % 16) return MMFS_E_ALIGN;
     // token rows of off_q / att_q: packed, or ld elements apart (columns of one wider matrix); vector loads of P
     // (2 P) elements need the rows aligned like the packed ones
     if (ld_off == 0) ld_off = H * 2 * P;
@@ -966,51 +1005,65 @@ int mmfs_sample_forward_heads_shared(int dtype, const void *value, const int64_t
     int G = 4;
     while (G < d.L) G *= 2;                                                 // the plan kernel's lane-group width
     hipStream_t st = (hipStream_t)stream;
-    auto go = [&](auto tag_t, auto tag_lpi, auto tag_p) {
+    auto go = [&](auto tag_t, auto tag_b, auto tag_lpi, auto tag_p) {
         typedef decltype(tag_t) T;
+        typedef decltype(tag_b) BT;
         constexpr int LPI = decltype(tag_lpi)::value, PP = decltype(tag_p)::value;
         constexpr int QPB = kThreads / LPI;
         Dims dd = d;
         dd.q_tiles = (d.Nq + QPB - 1) / QPB;
         const int64_t blocks = (int64_t)d.B * dd.q_tiles * d.H;
         if (blocks > 0x7fffffffLL) return (int)MMFS_E_DIMS;
-        hipLaunchKernelGGL((mmfs_sample_fwd<T, LPI, PP>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
-                           (const T *)value, shapes, start, (const T *)off_q, (const T *)att_q,
+        hipLaunchKernelGGL((mmfs_sample_fwd<T, LPI, PP, BT>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+                           (const BT *)value, shapes, start, (const T *)off_q, (const T *)att_q,
                            (const T *)off_tab, (const T *)att_tab, relpos, ref, ratios, (T *)out, sink, dd, pd, G,
-                           (const T *)token);
+                           (const T *)token, scale);
         return (int)hipGetLastError();
     };
-    auto go_decode = [&](auto tag_t, auto tag_lpi, auto tag_p) {
+    auto go_decode = [&](auto tag_t, auto tag_b, auto tag_lpi, auto tag_p) {
         typedef decltype(tag_t) T;
+        typedef decltype(tag_b) BT;
         constexpr int LPI = decltype(tag_lpi)::value, PP = decltype(tag_p)::value;
         if constexpr (LPI <= 32) {
-            hipLaunchKernelGGL((mmfs_sample_decode<T, LPI, PP>), dim3((unsigned)(d.B * d.Nq * d.H)), dim3(64), 0, st,
-                               (const T *)value, shapes, start, (const T *)off_q, (const T *)att_q,
+            hipLaunchKernelGGL((mmfs_sample_decode<T, LPI, PP, BT>), dim3((unsigned)(d.B * d.Nq * d.H)), dim3(64), 0, st,
+                               (const BT *)value, shapes, start, (const T *)off_q, (const T *)att_q,
                                (const T *)off_tab, (const T *)att_tab, relpos, ref, ratios, (T *)out, sink, d, pd, G,
-                               (const T *)token);
+                               (const T *)token, scale);
             return (int)hipGetLastError();
         } else {
             return (int)MMFS_E_UNSUPPORTED;
         }
     };
     const bool decode = sample_groups(Lq, d.K, d.L, lpi) > 1;
-    auto by_p = [&](auto tag_t, auto tag_lpi) {
+    auto by_p = [&](auto tag_t, auto tag_b, auto tag_lpi) {
         if (decode) {
-            if (P == 4) return go_decode(tag_t, tag_lpi, std::integral_constant<int, 4>());
-            return go_decode(tag_t, tag_lpi, std::integral_constant<int, 8>());
+            if (P == 4) return go_decode(tag_t, tag_b, tag_lpi, std::integral_constant<int, 4>());
+            return go_decode(tag_t, tag_b, tag_lpi, std::integral_constant<int, 8>());
         }
-        if (P == 4) return go(tag_t, tag_lpi, std::integral_constant<int, 4>());
-        return go(tag_t, tag_lpi, std::integral_constant<int, 8>());
+        if (P == 4) return go(tag_t, tag_b, tag_lpi, std::integral_constant<int, 4>());
+        return go(tag_t, tag_b, tag_lpi, std::integral_constant<int, 8>());
     };
     auto by_lpi = [&](auto tag_t) {
+        typedef decltype(tag_t) T;
+        if (fp8) {                                                         // (16 channels per lane: D = 16 .. 256)
+            const fp8e4m3_t b{};
+            switch (lpi) {
+                case 1: return by_p(tag_t, b, std::integral_constant<int, 1>());
+                case 2: return by_p(tag_t, b, std::integral_constant<int, 2>());
+                case 4: return by_p(tag_t, b, std::integral_constant<int, 4>());
+                case 8: return by_p(tag_t, b, std::integral_constant<int, 8>());
+                default: return by_p(tag_t, b, std::integral_constant<int, 16>());
+            }
+        }
+        const T b{};
         switch (lpi) {
-            case 1: return by_p(tag_t, std::integral_constant<int, 1>());
-            case 2: return by_p(tag_t, std::integral_constant<int, 2>());
-            case 4: return by_p(tag_t, std::integral_constant<int, 4>());
-            case 8: return by_p(tag_t, std::integral_constant<int, 8>());
-            case 16: return by_p(tag_t, std::integral_constant<int, 16>());
-            case 32: return by_p(tag_t, std::integral_constant<int, 32>());
-            default: return by_p(tag_t, std::integral_constant<int, 64>());
+            case 1: return by_p(tag_t, b, std::integral_constant<int, 1>());
+            case 2: return by_p(tag_t, b, std::integral_constant<int, 2>());
+            case 4: return by_p(tag_t, b, std::integral_constant<int, 4>());
+            case 8: return by_p(tag_t, b, std::integral_constant<int, 8>());
+            case 16: return by_p(tag_t, b, std::integral_constant<int, 16>());
+            case 32: return by_p(tag_t, b, std::integral_constant<int, 32>());
+            default: return by_p(tag_t, b, std::integral_constant<int, 64>());
         }
     };
     if (dtype == MMFS_F32) return by_lpi(float());

@@ -128,6 +128,36 @@ int mmfs_msda_forward_shared(int dtype, const void *value, const int64_t *shapes
     return (int)mmfs::forward(dtype, value, shapes, start, loc, attn, out, d, st, algo);
 }
 
+int mmfs_msda_forward_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                          const void *loc, const void *attn, void *out,
+                          int64_t B, int64_t Bv, int layout, int64_t S, int64_t H, int64_t D,
+                          int64_t L, int64_t Nq, int64_t P, void *stream)
+{
+    const int es = elem_size(dtype);
+    if (!es || dtype == MMFS_F64) return MMFS_E_DTYPE;
+    mmfs::Dims d;
+    const int rc = make_dims(B, S, H, D, L, Nq, P, &d);
+    if (rc) return rc;
+    if (Bv <= 0 || B % Bv != 0) return MMFS_E_DIMS;
+    if (layout != MMFS_BANK_TILE && layout != MMFS_BANK_INTERLEAVE) return MMFS_E_UNSUPPORTED;
+    if (!mmfs::fwd_fp8_supported(d)) return MMFS_E_UNSUPPORTED;             // (D = 16 * 2^k, k <= 4; D = 0 included)
+    if (B > 0) {
+        d.Bv = (int)Bv;
+        d.vdiv = layout == MMFS_BANK_INTERLEAVE ? (int)(B / Bv) : 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_out = B * Nq * H * D;
+    if (n_out == 0) return MMFS_OK;
+    if (!out) return MMFS_E_NULLPTR;
+    if (d.K == 0 || S == 0)                          // nothing to sample: the op's value is 0
+        return (int)mmfs::zero_fill(out, (size_t)n_out * es, st);
+    if (!q || !scale || !shapes || !start || !loc || !attn) return MMFS_E_NULLPTR;
+    // 16 channels (16 bytes of q, 64 of scale) per lane; out in 16-byte pieces
+    if (misaligned(q, 16) || misaligned(scale, 16) || misaligned(out, 16) || misaligned(loc, es) || misaligned(attn, es))
+        return MMFS_E_ALIGN;
+    return (int)mmfs::forward_fp8(dtype, q, scale, shapes, start, loc, attn, out, d, st);
+}
+
 static bool use_tiled(int dtype, const mmfs::Dims &d, unsigned flags)
 {
     if (flags & MMFS_BWD_FORCE_ATOMIC) return false;

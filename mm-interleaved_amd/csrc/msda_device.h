@@ -92,6 +92,76 @@ template <> struct Vec16<half_t> {
     }
 };
 
+// OCP e4m3 (e4m3fn, not the fnuz variant) -- the inference-only value bank (include/mmfs_msda.h "fp8 bank"): a byte,
+// read 16 channels per 16-byte lane load and widened two at a time by v_cvt_pk_f32_fp8.  Never an output type.
+struct fp8e4m3_t { uint8_t bits; };
+template <typename T> struct is_fp8 { static constexpr bool value = false; };
+template <> struct is_fp8<fp8e4m3_t> { static constexpr bool value = true; };
+
+template <> struct Vec16<fp8e4m3_t> {
+    static constexpr int N = 16;
+    static __device__ __forceinline__ void up(uint32_t w, float *o) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+        const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+        o[0] = lo[0]; o[1] = lo[1]; o[2] = hi[0]; o[3] = hi[1];
+    }
+    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[16]) {
+        up(r.x, o); up(r.y, o + 4); up(r.z, o + 8); up(r.w, o + 12);
+    }
+};
+
+// A lane's VEC channels of an output / token row of type T, in 16-byte pieces (one piece when the bank type is T)
+template <typename T, int VEC>
+__device__ __forceinline__ void load_vec(const T *p, float (&o)[VEC])
+{
+    typedef Vec16<T> W;
+    static_assert(VEC % W::N == 0, "whole 16-byte pieces");
+#pragma unroll
+    for (int j = 0; j < VEC / W::N; ++j) {
+        float part[W::N];
+        W::unpack(*reinterpret_cast<const uint4 *>(p + j * W::N), part);
+#pragma unroll
+        for (int i = 0; i < W::N; ++i) o[j * W::N + i] = part[i];
+    }
+}
+
+template <typename T, int VEC, bool STREAM>
+__device__ __forceinline__ void store_vec(T *p, const float (&v)[VEC])
+{
+    typedef Vec16<T> W;
+    static_assert(VEC % W::N == 0, "whole 16-byte pieces");
+#pragma unroll
+    for (int j = 0; j < VEC / W::N; ++j) {
+        float part[W::N];
+#pragma unroll
+        for (int i = 0; i < W::N; ++i) part[i] = v[j * W::N + i];
+        const uint4 r = W::pack(part);
+        if (STREAM) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(p + j * W::N);
+            __builtin_nontemporal_store(r.x, o); __builtin_nontemporal_store(r.y, o + 1);
+            __builtin_nontemporal_store(r.z, o + 2); __builtin_nontemporal_store(r.w, o + 3);
+        } else {
+            *reinterpret_cast<uint4 *>(p + j * W::N) = r;
+        }
+    }
+}
+
+// fp8 bank: multiply a lane's fp32 sums by their channels' scales (scale [Bv, H*D]; the row's 16-channel piece is
+// 64-byte aligned).  A 16-bit bank has no scale and this is nothing.
+template <typename BT, int VEC>
+__device__ __forceinline__ void apply_scale(float (&acc)[VEC], const float *__restrict__ scale, int64_t off)
+{
+    if constexpr (is_fp8<BT>::value) {
+        const uint4 *s = reinterpret_cast<const uint4 *>(scale + off);
+#pragma unroll
+        for (int j = 0; j < VEC / 4; ++j) {
+            const uint4 r = s[j];
+            acc[4 * j] *= __uint_as_float(r.x); acc[4 * j + 1] *= __uint_as_float(r.y);
+            acc[4 * j + 2] *= __uint_as_float(r.z); acc[4 * j + 3] *= __uint_as_float(r.w);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- bilinear tap
 // One sample's 2x2 footprint.  row[i] is the pixel index inside the whole value
 // tensor's S axis (level start included), or -1 when the corner is outside the map

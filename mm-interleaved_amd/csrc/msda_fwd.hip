@@ -38,13 +38,16 @@ struct alignas(16) FwdRec {
 // BUF = true : row reads through a buffer descriptor (32-bit offsets, hardware zero for
 //              corners outside the map)               -- slabs < 2 GiB, the normal case
 // BUF = false: 64-bit flat addresses, clamped read + select
-template <typename T, int LPI, bool BUF>
+//
+// BT is the bank's type: T, or fp8e4m3_t for the inference-only fp8 bank (16 channels per lane, its fp32 scale per
+// (bank row, channel) applied once at the store -- include/mmfs_msda.h "fp8 bank"); loc / attn / out stay T.
+template <typename T, int LPI, bool BUF, typename BT>
 __global__ void __launch_bounds__(kThreads)
-msda_fwd_vec(const T *__restrict__ value, const int64_t *__restrict__ shapes,
+msda_fwd_vec(const BT *__restrict__ value, const int64_t *__restrict__ shapes,
              const int64_t *__restrict__ start, const T *__restrict__ loc,
-             const T *__restrict__ attn, T *__restrict__ out, const Dims d)
+             const T *__restrict__ attn, T *__restrict__ out, const Dims d, const float *__restrict__ vscale)
 {
-    typedef Vec16<T> V;
+    typedef Vec16<BT> V;
     constexpr int VEC = V::N;
     constexpr int QPB = kThreads / LPI;           // queries per block
     constexpr int KC = (kRecsPerBlock / QPB) > kUnroll ? (kRecsPerBlock / QPB) : kUnroll;  // samples per query per chunk (pow2)
@@ -70,12 +73,12 @@ msda_fwd_vec(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int Ksel = d.K;
 
     const int64_t HD = (int64_t)d.H * d.D;
-    const T *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;   // this (b, h)
-    const T *vbase = slab + lig * VEC;
-    const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
+    const BT *slab = value + ((int64_t)value_row(d, bc.b) * d.S) * HD + (int64_t)bc.h * d.D;   // this (b, h)
+    const BT *vbase = slab + lig * VEC;
+    const uint32_t row_bytes = (uint32_t)(HD * sizeof(BT));
     const uint32_t lane_off = (uint32_t)(lig * 16);
     __amdgpu_buffer_rsrc_t rsrc;
-    if (BUF) rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)bc.h * d.D) * (int64_t)sizeof(T));
+    if (BUF) rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)bc.h * d.D) * (int64_t)sizeof(BT));
 
     float acc[VEC];
 #pragma unroll
@@ -235,7 +238,8 @@ msda_fwd_vec(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     }
     if (q_ok) {
         T *o = out + (((int64_t)bc.b * d.Nq + q) * d.H + bc.h) * d.D + lig * VEC;
-        store16_stream(o, V::pack(acc));                 // (the output is not read again in the step: profiles/r03_experiments.md r03j)
+        apply_scale<BT, VEC>(acc, vscale, (int64_t)value_row(d, bc.b) * HD + (int64_t)bc.h * d.D + lig * VEC);
+        store_vec<T, VEC, true>(o, acc);                 // (the output is not read again in the step: profiles/r03_experiments.md r03j)
     }
 }
 
@@ -275,22 +279,23 @@ msda_fwd_scalar(const T *__restrict__ value, const int64_t *__restrict__ shapes,
 }
 
 // ---------------------------------------------------------------- launchers
-template <typename T, int LPI>
+template <typename T, int LPI, typename BT = T>
 static hipError_t launch_vec(const void *value, const int64_t *shapes, const int64_t *start,
-                             const void *loc, const void *attn, void *out, Dims d, hipStream_t st)
+                             const void *loc, const void *attn, void *out, Dims d, hipStream_t st,
+                             const float *vscale = nullptr)
 {
     constexpr int QPB = kThreads / LPI;
     d.q_tiles = (d.Nq + QPB - 1) / QPB;
     const int64_t blocks = (int64_t)d.B * d.q_tiles * d.H;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     // one (batch) slab of value must be addressable with 31-bit byte offsets for the buffer path
-    const bool buf = (int64_t)d.S * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes;
+    const bool buf = (int64_t)d.S * d.H * d.D * (int64_t)sizeof(BT) <= kMaxSlabBytes;
     if (buf)
-        hipLaunchKernelGGL((msda_fwd_vec<T, LPI, true>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
-                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d);
+        hipLaunchKernelGGL((msda_fwd_vec<T, LPI, true, BT>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+                           (const BT *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, vscale);
     else
-        hipLaunchKernelGGL((msda_fwd_vec<T, LPI, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
-                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d);
+        hipLaunchKernelGGL((msda_fwd_vec<T, LPI, false, BT>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+                           (const BT *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, vscale);
     return hipGetLastError();
 }
 
@@ -335,6 +340,37 @@ hipError_t forward(int dtype, const void *value, const int64_t *shapes, const in
         case 1: return dispatch_fwd<half_t>(value, shapes, start, loc, attn, out, d, st);
         case 2: return dispatch_fwd<bf16_t>(value, shapes, start, loc, attn, out, d, st);
         case 3: return launch_scalar<double>(value, shapes, start, loc, attn, out, d, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+bool fwd_fp8_supported(const Dims &d)
+{
+    const int lpi = d.D / 16;
+    return d.D % 16 == 0 && lpi >= 1 && lpi <= 16 && (lpi & (lpi - 1)) == 0;
+}
+
+template <typename T>
+static hipError_t dispatch_fwd_fp8(const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                                   const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
+{
+    switch (d.D / 16) {
+#define MMFS_CASE(n) case n: return launch_vec<T, n, fp8e4m3_t>(q, shapes, start, loc, attn, out, d, st, scale);
+        MMFS_CASE(1) MMFS_CASE(2) MMFS_CASE(4) MMFS_CASE(8) MMFS_CASE(16)
+#undef MMFS_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// fp8 bank: the row gather only (the matrix-core forwards stay 16-bit)
+hipError_t forward_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                       const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
+{
+    if (!fwd_fp8_supported(d)) return hipErrorInvalidValue;
+    switch (dtype) {
+        case 0: return dispatch_fwd_fp8<float>(q, scale, shapes, start, loc, attn, out, d, st);
+        case 1: return dispatch_fwd_fp8<half_t>(q, scale, shapes, start, loc, attn, out, d, st);
+        case 2: return dispatch_fwd_fp8<bf16_t>(q, scale, shapes, start, loc, attn, out, d, st);
         default: return hipErrorInvalidValue;
     }
 }

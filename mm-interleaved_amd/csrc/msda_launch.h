@@ -120,6 +120,12 @@ hipError_t cast_from_f32(int dtype, const float *src, void *dst, int64_t n, hipS
 // the workspace -- one replay in a few dozen, only the first run on a fresh device).  A kernel orders like a kernel.
 hipError_t zero_fill(void *p, size_t bytes, hipStream_t st);
 
+// fp8 bank (include/mmfs_msda.h "fp8 bank"): the row-gather forward on an e4m3 bank with fp32 scales [Bv, H*D]; loc / attn /
+// out of dtype 0..2.  Head widths D = 16 * 2^k, k <= 4.                                   [msda_fwd.hip]
+bool fwd_fp8_supported(const Dims &d);
+hipError_t forward_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
+                       const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st);
+
 // grad_value for a level table the device-side check of the sorted backward refused (its plan's verdict is read on the
 // device from the workspace; nothing happens for a table it served): the reference's float-atomic scatter.
 // acc: refused_table_scratch_bytes of fp32 image for 16-bit storage (ignored for fp32).          [msda_bwd_refused.hip]

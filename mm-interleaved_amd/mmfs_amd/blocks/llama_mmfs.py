@@ -105,7 +105,7 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
         self._gate_fold = FoldedLinear()
 
     def forward(self, hidden_states, vision_hidden_states=None, cross_attention_mask=None, value=None, image_ranks=None,
-                residual=None, bank_repeat=None):
+                residual=None, bank_repeat=None, value_scale=None):
         """hidden_states [B, Lq, hidden]; vision_hidden_states [B, n, sum hw, image_embed_dim];
         cross_attention_mask [B, Lq', n] (float, 1 = visible) -> [B, Lq, hidden].
         ``value`` (an addition): this layer's ``value_proj(norm2(vision_hidden_states))`` [B, n, sum hw, d_inner] as
@@ -115,15 +115,21 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
         statement (modeling_llama_mmfs.py:700-717), which without gradients rides in the output projection's kernel.
         ``bank_repeat`` (a fourth, ``MMFS.forward``): None, or "interleave" / "tile" when ``vision_hidden_states`` / ``value``
         have the batch Bv of a bank shared by the B = g * Bv token rows -- beam search hands the un-expanded bank (HF's
-        ``repeat_interleave(num_beams, 0)`` order: "interleave")."""
+        ``repeat_interleave(num_beams, 0)`` order: "interleave").
+        ``value_scale`` (a fifth, ``MMFS.forward``): the scales of an fp8 ``value`` (``ProjectedBank.scales``) -- inference only."""
         args = (hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual, bank_repeat)
+        if value_scale is not None:
+            if self.training:
+                raise RuntimeError("LlamaMMFSAttention: the fp8 bank is inference only")
+            return self._forward(*args, value_scale=value_scale)
         if self.graph_training_calls and self.training:
             # a training step's call as HIP graphs once its shapes have been seen a few times (mmfs_amd/graphed.py) -- the
             # forward with its saved activations, the backward; and the no-grad forward of a checkpointing caller
             return graphed_call(self, self._forward, args, recompute=False, plain=lambda: self._forward(*args))
         return self._forward(*args)
 
-    def _forward(self, hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual, bank_repeat=None):
+    def _forward(self, hidden_states, vision_hidden_states, cross_attention_mask, value, image_ranks, residual, bank_repeat=None,
+                 value_scale=None):
         hidden_states = self.norm1(hidden_states)
         if value is None:
             vision_hidden_states = self.norm2(vision_hidden_states)
@@ -138,17 +144,19 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
             return self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                              input_spatial_shapes=shapes, input_level_start_index=start, input_padding_mask=None,
                              attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
-                             output_weights=folded, output_residual=residual, bank_repeat=bank_repeat)
+                             output_weights=folded, output_residual=residual, bank_repeat=bank_repeat,
+                             value_scale=value_scale)
         if residual is not None:
             # the gate and the residual sum ride with the output projection (``GatedProjectionFunction`` with gradients)
             return self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                              input_spatial_shapes=shapes, input_level_start_index=start, input_padding_mask=None,
                              attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
-                             output_gate=self._gate(), output_residual=residual, bank_repeat=bank_repeat)
+                             output_gate=self._gate(), output_residual=residual, bank_repeat=bank_repeat,
+                             value_scale=value_scale)
         out = self.attn(query=hidden_states, reference_points=ref, input_flatten=vision_hidden_states,
                         input_spatial_shapes=shapes, input_level_start_index=start,
                         input_padding_mask=None, attention_mask=cross_attention_mask, value=value, image_ranks=image_ranks,
-                        bank_repeat=bank_repeat)
+                        bank_repeat=bank_repeat, value_scale=value_scale)
         return out * self._gate()
 
     def _gate(self):
@@ -165,10 +173,12 @@ class LlamaMMFSAttention(CacheInvalidation, nn.Module):
 
 class ProjectedBank:
     """``value_proj_k(norm2_k(bank))`` of every MMFS layer of a decoder for one feature bank: ``values[k]`` is
-    layer k's [B, n, sum hw, d_inner] (contiguous).  Made by ``LlamaMMFSSchedule.project``."""
+    layer k's [B, n, sum hw, d_inner] (contiguous).  Made by ``LlamaMMFSSchedule.project``.  ``scales``: None, or with
+    ``values`` fp8 banks (``LlamaMMFSSchedule.kept_bank_dtype``) their fp32 scales, ``scales[k]`` [B, d_inner]: layer k is
+    then called with ``value=values[k], value_scale=scales[k]``."""
 
-    def __init__(self, values, bank, source=None, weights=None, bank_repeat=None):
-        self.values, self.bank = values, bank
+    def __init__(self, values, bank, source=None, weights=None, bank_repeat=None, scales=None):
+        self.values, self.bank, self.scales = values, bank, scales
         self.bank_repeat = bank_repeat                   # how the caller said the bank serves its token rows (``project``)
         self.source, self.weights = source, weights      # identity cache: (tensor, version), parameter signature
 
@@ -198,6 +208,9 @@ class LlamaMMFSSchedule:
     Differentiable: gradients reach every ``W_k``, ``b_k``, ``g_k`` and the features."""
 
     cache_projected_bank = True
+    # Opt-in, inference only: ``torch.float8_e4m3fn`` keeps the projections of a no-grad / eval call as fp8 banks with one
+    # fp32 scale per (bank row, channel), all layers quantised in one launch (DESIGN.md 4.10; ``MMFSNet.kept_bank_dtype``).
+    kept_bank_dtype = None
 
     def __init__(self, layers):
         self.layers = list(layers)
@@ -223,7 +236,7 @@ class LlamaMMFSSchedule:
         return (cache_epoch(),) + tuple((p.data_ptr(), tensor_version(p)) for l in self.layers
                                         for p in (l.norm2.weight, l.attn.value_proj.weight, l.attn.value_proj.bias) if p is not None)
 
-    def _project(self, bank):
+    def _project(self, bank, bank_dtype=None):
         norm = self.layers[0].norm2
         var = bank.to(torch.float32).pow(2).mean(-1, keepdim=True)
         xhat = bank * torch.rsqrt(var + norm.variance_epsilon)
@@ -234,6 +247,13 @@ class LlamaMMFSSchedule:
         y = torch.matmul(xhat.reshape(1, -1, xhat.shape[-1]).to(wt.dtype), wt)         # [n_layers, tokens, d_inner]
         if self.layers[0].attn.value_proj.bias is not None:
             y = y + torch.stack([l.attn.value_proj.bias for l in self.layers])[:, None, :]
+        if bank_dtype is not None:
+            import MultiScaleDeformableAttention as MSDA
+            if bank_dtype != MSDA.FP8_BANK_DTYPE:
+                raise ValueError(f"kept_bank_dtype: None or torch.float8_e4m3fn, not {bank_dtype}")
+            K, B, width = y.shape[0], bank.shape[0], y.shape[-1]
+            q, scale = MSDA.quantize_bank_fp8(y.reshape(K, B, -1, 1, width))          # every layer in one launch
+            return [q[k].view(*bank.shape[:-1], -1) for k in range(K)], list(scale.unbind(0))
         return [y[k].view(*bank.shape[:-1], -1) for k in range(len(self.layers))]
 
     def project(self, vision_hidden_states, bank_repeat=None):
@@ -248,11 +268,16 @@ class LlamaMMFSSchedule:
                                  vision_hidden_states, bank_repeat=bank_repeat)
         keep = self.cache_projected_bank and not torch.is_grad_enabled() and not any(l.training for l in self.layers)
         sig = self._weights()
+        kept_dtype = self.kept_bank_dtype if keep else None
         if (keep and self._projected is not None and self._projected.matches(vision_hidden_states, sig)
-                and self._projected.bank_repeat == bank_repeat):
+                and self._projected.bank_repeat == bank_repeat and (self._projected.scales is not None) == (kept_dtype is not None)):
             return self._projected
-        proj = ProjectedBank(self._project(vision_hidden_states), vision_hidden_states,
-                             (vision_hidden_states, tensor_version(vision_hidden_states)), sig, bank_repeat=bank_repeat)
+        if kept_dtype is not None:
+            values, scales = self._project(vision_hidden_states, kept_dtype)
+        else:
+            values, scales = self._project(vision_hidden_states), None
+        proj = ProjectedBank(values, vision_hidden_states, (vision_hidden_states, tensor_version(vision_hidden_states)), sig,
+                             bank_repeat=bank_repeat, scales=scales)
         self._projected = proj if keep else None
         return proj
 

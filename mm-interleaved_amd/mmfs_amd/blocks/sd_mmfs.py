@@ -206,7 +206,7 @@ class MMFSBlock(CacheInvalidation, nn.Module):
                 and self._conv_is_pointwise() and layout_supported(sample))
 
     def _inner(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None,
-               bank_repeat=None):
+               bank_repeat=None, value_scale=None):
         B, C, H, W = sample.shape
         if value is None and normed is not None:
             # the bank already normalised WITHOUT the affine (MMFSNet, shared by its blocks): this block's affine folds
@@ -237,7 +237,7 @@ class MMFSBlock(CacheInvalidation, nn.Module):
             folded = self._conv_fold.get(proj.weight, proj.bias, self.conv.weight.view(C, C), self.conv.bias)
         out = self.mmfs(query, ref, self.feat_norm(ms_feat) if value is None else ms_feat, shapes, start,
                         input_padding_mask=None, attention_mask=ms_feat_mask, value=value, image_ranks=image_ranks,
-                        output_weights=folded, bank_repeat=bank_repeat)
+                        output_weights=folded, bank_repeat=bank_repeat, value_scale=value_scale)
         # the zero-initialised 1x1 convolution (sd_mmfs.py:88-94, 146) is a per-token linear map:
         # applied on the token-major tensor it is one GEMM each way (the convolution library's 1x1
         # backward took 0.45 ms per block at B=8, the GEMMs take ~0.05)
@@ -254,7 +254,7 @@ class MMFSBlock(CacheInvalidation, nn.Module):
         return out if residual is None else residual + out
 
     def forward(self, sample, ms_feat, ms_feat_mask, spatial_shapes, value=None, image_ranks=None, residual=None, normed=None,
-                bank_repeat=None):
+                bank_repeat=None, value_scale=None):
         """sample [B, C_q, H, W]; ms_feat [B, n, sum_l H_l*W_l, C_v]; ms_feat_mask [B, n];
         spatial_shapes: the levels of ONE image, list of (H_l, W_l)  ->  [B, C_q, H, W].
         ``value`` (an addition to sd_mmfs.py:121-146): this block's
@@ -265,9 +265,12 @@ class MMFSBlock(CacheInvalidation, nn.Module):
         (another): ``layer_norm(ms_feat)`` without the affine, when the caller has it -- the block then folds its
         ``feat_norm`` affine into its value projection (inside its checkpoint: the projected bank is not kept);
         ``bank_repeat`` (another, ``MMFS.forward``): ``ms_feat`` / ``value`` / ``normed`` are a bank of batch Bv shared by the
-        B = g * Bv rows of ``sample`` / ``ms_feat_mask`` -- "tile" (classifier-free guidance) or "interleave"."""
+        B = g * Bv rows of ``sample`` / ``ms_feat_mask`` -- "tile" (classifier-free guidance) or "interleave".
+        ``value_scale`` (another, ``MMFS.forward``): the scales of an fp8 ``value`` -- inference only."""
         spatial_shapes = [tuple(int(v) for v in s) for s in spatial_shapes]
         if self.gradient_checkpointing and self.training:
+            if value_scale is not None:
+                raise RuntimeError("MMFSBlock: the fp8 bank is inference only (training / checkpointing never takes it)")
             # the op is stateless and re-entrant: the forward is simply re-run in backward
             # (a projected ``value`` is an input of the checkpoint: kept, not recomputed)
             # (``residual`` is an input the caller holds anyway -- for ``MMFSNet`` the sample itself)
@@ -291,7 +294,8 @@ class MMFSBlock(CacheInvalidation, nn.Module):
                 return graphed_call(self, self._inner, (sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks,
                                                         residual, normed, bank_repeat), recompute=not keep, plain=plain)
             return plain()
-        return self._inner(sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks, residual, normed, bank_repeat)
+        return self._inner(sample, ms_feat, ms_feat_mask, spatial_shapes, value, image_ranks, residual, normed, bank_repeat,
+                           value_scale)
 
 
 class ProjectedFeatures:
@@ -299,11 +303,13 @@ class ProjectedFeatures:
     ``values[k]`` is block k's [B, n, sum_l H_l*W_l, d_inner] (the mid block last).  Made by
     ``MMFSNet.project_features``; accepted by ``MMFSNet.forward`` in place of the feature list.  ``bank_repeat``: None,
     or "tile" when the projections hold the first half of a bank whose two halves were equal (``dedupe_repeated_bank``):
-    ``MMFSNet.forward`` then serves the doubled batch from them."""
+    ``MMFSNet.forward`` then serves the doubled batch from them.  ``scales``: None, or with ``values`` fp8 banks
+    (``MMFSNet.kept_bank_dtype``) their fp32 scales, ``scales[k]`` [B, d_inner] (MultiScaleDeformableAttention.quantize_bank_fp8)."""
 
-    def __init__(self, values, bank, shapes, sources=None, weights=None, bank_repeat=None):
+    def __init__(self, values, bank, shapes, sources=None, weights=None, bank_repeat=None, scales=None):
         self.values, self.bank, self.shapes = values, bank, shapes
         self.bank_repeat = bank_repeat
+        self.scales = scales
         # what it was computed from (identity cache of MMFSNet.forward): the feature tensors with
         # their versions, and (storage, version) of every parameter that went in
         self.sources, self.weights = sources, weights
@@ -342,6 +348,11 @@ class MMFSNet(CacheInvalidation, nn.Module):
     # cache then holds it -- and if the halves are equal only the first half is projected and the blocks run with
     # ``bank_repeat="tile"``.  Off by default: fewer projected rows may select another GEMM kernel (other roundings).
     dedupe_repeated_bank = False
+    # Opt-in, inference only: ``torch.float8_e4m3fn`` keeps the eval / no-grad projections (the cache above) as fp8 banks with
+    # one fp32 scale per (bank row, channel), quantised once per bank in one launch: half the bytes the
+    # 13 samplers read in every denoising step, within 2^-4 |x| + 2^-10 scale of each projected value.  None: the
+    # projections keep the feature type.  Training, gradients and checkpointing never see it.
+    kept_bank_dtype = None
 
     def _project_once(self, mmfs_features):
         """Whether this training step keeps all blocks' projections of the bank (see ``project_once_in_training``)."""
@@ -419,11 +430,12 @@ class MMFSNet(CacheInvalidation, nn.Module):
                    and type(b.mmfs.value_proj) is nn.Linear and hook_free(b.mmfs.value_proj) and hook_free(b.feat_norm)
                    for b in blocks)
 
-    def project_features(self, mmfs_features, dedupe=False):
+    def project_features(self, mmfs_features, dedupe=False, bank_dtype=None):
         """Per level [B, n, C, h_l, w_l] -> ``ProjectedFeatures``: the bank normalised ONCE, then
         every block's value projection with its LayerNorm affine folded into the weights.  ``dedupe``: when B is even and
         every level's two halves are equal, project the first half only (``bank_repeat = "tile"``; see
-        ``dedupe_repeated_bank``)."""
+        ``dedupe_repeated_bank``).  ``bank_dtype``: None, or ``torch.float8_e4m3fn`` -- the projections quantised to fp8
+        banks with their scales (see ``kept_bank_dtype``; no gradients)."""
         sources = [(f, tensor_version(f)) for f in mmfs_features]
         repeat = None
         if dedupe and self._halves_equal(mmfs_features):
@@ -433,7 +445,29 @@ class MMFSNet(CacheInvalidation, nn.Module):
         bank = self._pack(mmfs_features)
         norm = self.mmfs_mid_block.feat_norm
         xhat = F.layer_norm(bank, norm.normalized_shape, None, None, norm.eps)
+        if bank_dtype is not None:
+            values, scales = self._project_all_fp8(xhat, bank_dtype)
+            return ProjectedFeatures(values, bank, shapes, sources, self._projection_weights(), bank_repeat=repeat,
+                                     scales=scales)
         return ProjectedFeatures(self._project_all(xhat), bank, shapes, sources, self._projection_weights(), bank_repeat=repeat)
+
+    def _project_all_fp8(self, xhat, bank_dtype):
+        """``_project_all`` (the same operations, so the same bits before quantisation) kept as fp8 banks: all blocks'
+        projections are ONE [n_blocks, B, n*hw, d_inner] buffer and are quantised in one launch."""
+        import MultiScaleDeformableAttention as MSDA
+        if bank_dtype != MSDA.FP8_BANK_DTYPE:
+            raise ValueError(f"kept_bank_dtype: None or torch.float8_e4m3fn, not {bank_dtype}")
+        if torch.is_grad_enabled() and (xhat.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("MMFSNet: the fp8 bank is inference only (project under torch.no_grad())")
+        blocks = self._blocks()
+        wt = torch.stack([(b.mmfs.value_proj.weight * b.feat_norm.weight).t() for b in blocks])
+        bias = torch.stack([F.linear(b.feat_norm.bias, b.mmfs.value_proj.weight, b.mmfs.value_proj.bias) for b in blocks])
+        x = xhat.reshape(-1, xhat.shape[-1]).to(wt.dtype)
+        y = torch.matmul(x[None], wt)                                  # (as _ProjectAll.forward)
+        y += bias[:, None, :]
+        K, B, rows, width = y.shape[0], xhat.shape[0], xhat.shape[1] * xhat.shape[2], y.shape[-1]
+        q, scale = MSDA.quantize_bank_fp8(y.view(K, B, rows, 1, width))
+        return [v.view(*xhat.shape[:-1], width) for v in q.unbind(0)], list(scale.unbind(0))
 
     @staticmethod
     def _halves_equal(mmfs_features):
@@ -500,16 +534,24 @@ class MMFSNet(CacheInvalidation, nn.Module):
         if proj is None and self.fused_schedule and self._can_fuse() and not ckpt:
             keep = self.cache_projected_features and not torch.is_grad_enabled() and not self.training
             proj = self.__dict__.get("_projected") if keep else None
-            if proj is None or not proj.matches(mmfs_features, self._projection_weights()):
+            kept_dtype = self.kept_bank_dtype if keep else None
+            if (proj is None or not proj.matches(mmfs_features, self._projection_weights())
+                    or (proj.scales is not None) != (kept_dtype is not None)):
                 dedupe = self.dedupe_repeated_bank and bank_repeat is None and not self.training and not torch.is_grad_enabled()
-                proj = self.project_features(mmfs_features, dedupe=True) if dedupe else self.project_features(mmfs_features)
+                if kept_dtype is not None:
+                    proj = self.project_features(mmfs_features, dedupe=dedupe, bank_dtype=kept_dtype)
+                else:
+                    proj = self.project_features(mmfs_features, dedupe=True) if dedupe else self.project_features(mmfs_features)
             if keep:
                 self.__dict__["_projected"] = proj
             else:
                 self.__dict__.pop("_projected", None)
         normed = None
+        scales = [None] * (len(self.mmfs_down_blocks) + 1)
         if proj is not None:
             bank, shapes, values = proj.bank, proj.shapes, proj.values
+            if proj.scales is not None:
+                scales = proj.scales
             if bank_repeat is None:
                 bank_repeat = proj.bank_repeat
         else:
@@ -525,8 +567,8 @@ class MMFSNet(CacheInvalidation, nn.Module):
         # (the images' ranks among the visible ones depend on the mask only: once for the 13 blocks)
         ranks = self.mmfs_mid_block.mmfs._image_relpos(mmfs_mask, 1) if mmfs_mask.dim() == 2 else None
         new_res = tuple(blk(r, bank, mmfs_mask, shapes, value=v, image_ranks=ranks, residual=r, normed=normed,
-                            bank_repeat=bank_repeat)
-                        for r, blk, v in zip(down_block_res_samples, self.mmfs_down_blocks, values))
+                            bank_repeat=bank_repeat, value_scale=sc)
+                        for r, blk, v, sc in zip(down_block_res_samples, self.mmfs_down_blocks, values, scales))
         sample = self.mmfs_mid_block(sample, bank, mmfs_mask, shapes, value=values[-1], image_ranks=ranks, residual=sample,
-                                     normed=normed, bank_repeat=bank_repeat)
+                                     normed=normed, bank_repeat=bank_repeat, value_scale=scales[-1])
         return sample, new_res

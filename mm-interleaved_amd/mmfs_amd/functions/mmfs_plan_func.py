@@ -35,6 +35,9 @@ _lib.mmfs_plan_forward_heads.restype = _int
 _lib.mmfs_plan_forward_heads.argtypes = [_int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 7 + [_i64] * 9 + [_vp]
 _lib.mmfs_plan_backward_heads.restype = _int
 _lib.mmfs_plan_backward_heads.argtypes = [_int] + [_vp] * 8 + [_vp, _vp, _i64, _i64, _int, _vp, _vp, _i64, _i64] + [_i64] * 9 + [_vp]
+_lib.mmfs_sample_forward_heads_fp8.restype = _int
+_lib.mmfs_sample_forward_heads_fp8.argtypes = ([_int] + [_vp] * 6 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
+                                               + [_i64] * 10 + [_vp])
 _lib.mmfs_sample_forward_groups.restype = _int
 _lib.mmfs_sample_forward_groups.argtypes = [_int] + [_i64] * 4
 _CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
@@ -176,12 +179,15 @@ def _token_rows(t, vec):
 def sample_forward_groups(dtype, Lq, D, nL, P):
     """Lane groups that share one query's samples in ``mmfs_sample_forward`` for this shape (include/mmfs_msda.h
     ``mmfs_sample_forward_groups``): 1 = summed in sample order, bit-identical to the two kernels; > 1 = a decode-sized
-    call (at most 8 queries per (sample, head)), equal within one rounding of the storage type; 0 = not served."""
+    call (at most 8 queries per (sample, head)), equal within one rounding of the storage type; 0 = not served.
+    ``dtype`` the bank's: an fp8 bank (16 channels per lane) takes the lanes of a bf16 bank of half the width."""
+    if dtype == MSDA.FP8_BANK_DTYPE:
+        return int(_lib.mmfs_sample_forward_groups(_CODE[torch.bfloat16], Lq, D // 2, nL, P)) if D % 16 == 0 else 0
     return int(_lib.mmfs_sample_forward_groups(_CODE[dtype], Lq, D, nL, P)) if dtype in _CODE else 0
 
 
 def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, relpos, ref, ratios, H, L, P, token=None,
-                        value_repeat=None):
+                        value_repeat=None, value_scale=None):
     """Plan -> sampler in ONE kernel (``mmfs_sample_forward`` in include/mmfs_msda.h):
     the locations / weights [N, Lq, H, n*L, P(, 2)] are never written.  Inference only (no autograd graph);
     bit-identical to ``MMFSPlanFunction`` + ``MSDeformAttnFunction`` (decode-sized calls: the same products with the fp32
@@ -190,8 +196,12 @@ def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, re
     the shape is outside the fused kernel's range (the caller then runs the two kernels).  ``token`` [.., H, D]
     (MMFS's ignore token): ``out + token * sink`` is formed inside the kernel, with the framework statement's roundings.
     ``value_repeat`` None, or "tile" / "interleave": ``value`` [Nv, S, H, D] is a bank shared by the N = g * Nv query
-    rows of ``off_q`` (MSDA.ms_deform_attn_forward; C ABI ``mmfs_sample_forward_heads_shared``)."""
-    dt = value.dtype
+    rows of ``off_q`` (MSDA.ms_deform_attn_forward; C ABI ``mmfs_sample_forward_heads_shared``).
+    ``value_scale``: with ``value`` an fp8 bank (MSDA.quantize_bank_fp8), its fp32 scales [Nv, H*D] (C ABI
+    ``mmfs_sample_forward_heads_fp8``); ``out`` then has ``off_q``'s type, the output type."""
+    fp8 = value.dtype == MSDA.FP8_BANK_DTYPE
+    MSDA._require(fp8 == (value_scale is not None), "an fp8 bank comes with its value_scale, and value_scale with an fp8 bank")
+    dt = off_q.dtype if fp8 else value.dtype              # (the output's type: loc / attn / out)
     if dt not in _CODE or off_q.dtype != dt or not value.is_cuda:
         return None
     Nv, S, Hh, D = value.shape
@@ -222,7 +232,17 @@ def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, re
             return None
         tok = MSDA._aligned(token.reshape(Hh, D).contiguous())
     with torch.cuda.device(dev):
-        if value_repeat is None:
+        if fp8:
+            MSDA._require(value_scale.dtype == torch.float32 and tuple(value_scale.shape) == (Nv, Hh * D) and value_scale.is_cuda,
+                          f"value_scale must be fp32 [{Nv}, {Hh * D}] on the bank's device")
+            value_scale = MSDA._aligned(value_scale.contiguous())
+            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads_fp8, _CODE[dt], value.data_ptr(),
+                              value_scale.data_ptr(), shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(),
+                              ld_off, ld_att, off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
+                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
+                              sink.data_ptr(), N, Nv, MSDA._VALUE_REPEAT[value_repeat or "tile"], S, Lq, Hh, D, L, P, n, M,
+                              Lr, Nr, MSDA._stream(dev))
+        elif value_repeat is None:
             rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads, _CODE[dt], value.data_ptr(),
                               shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
                               off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),

@@ -21,20 +21,31 @@ _bwd = torch.amp.custom_bwd(device_type="cuda")
 
 
 class MSDeformAttnFunction(Function):
+    @classmethod
+    def apply(cls, *args, **kwargs):
+        # (asked here: inside ``forward`` grad mode is off, and ``needs_input_grad`` does not know whether it was on)
+        if (isinstance(args[0], torch.Tensor) and args[0].dtype == MSDA.FP8_BANK_DTYPE and torch.is_grad_enabled()
+                and any(isinstance(t, torch.Tensor) and t.requires_grad for t in args[:5])):
+            raise RuntimeError("MSDeformAttnFunction: the fp8 bank is inference only -- no gradients through it "
+                               "(run under torch.no_grad() or keep the bank in 16 bits)")
+        return super().apply(*args, **kwargs)
+
     @staticmethod
     @_fwd
     def forward(ctx, value, value_spatial_shapes, value_level_start_index,
-                sampling_locations, attention_weights, im2col_step, lazy_zero_attn=False, value_repeat=None):
+                sampling_locations, attention_weights, im2col_step, lazy_zero_attn=False, value_repeat=None,
+                value_scale=None):
         # ``lazy_zero_attn`` is an addition to the reference's six arguments (see
         # MSDA.ms_deform_attn_backward): set by MMFS, whose softmax backward never looks at the
         # gradient of a weight that is exactly zero.  ``value_repeat`` another (MSDA.ms_deform_attn_forward):
-        # None, or "tile" / "interleave" when ``value`` is a bank of batch Bv shared by g * Bv query rows
+        # None, or "tile" / "interleave" when ``value`` is a bank of batch Bv shared by g * Bv query rows.
+        # ``value_scale`` a third: the scales of an fp8 ``value`` (MSDA.quantize_bank_fp8) -- inference only (``apply``)
         ctx.im2col_step = im2col_step
         ctx.lazy_zero_attn = bool(lazy_zero_attn)
         ctx.value_repeat = value_repeat
         output = MSDA.ms_deform_attn_forward(
             value, value_spatial_shapes, value_level_start_index,
-            sampling_locations, attention_weights, ctx.im2col_step, value_repeat=value_repeat)
+            sampling_locations, attention_weights, ctx.im2col_step, value_repeat=value_repeat, value_scale=value_scale)
         ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index,
                               sampling_locations, attention_weights)
         return output
@@ -48,7 +59,7 @@ class MSDeformAttnFunction(Function):
         grad_value, grad_loc, grad_attn = MSDA.ms_deform_attn_backward(
             value, shapes, start, loc, attn, grad_output, ctx.im2col_step, ctx.lazy_zero_attn,
             value_repeat=ctx.value_repeat)
-        return grad_value, None, None, grad_loc, grad_attn, None, None, None
+        return grad_value, None, None, grad_loc, grad_attn, None, None, None, None
 
 
 def ms_deform_attn_core_pytorch(value, value_spatial_shapes, sampling_locations, attention_weights):

@@ -43,7 +43,8 @@ class GraphedMMFSNet:
     ``g(sample, residuals)`` replays for new residuals of the same shapes and returns
     ``(sample', residuals')`` exactly like ``net(sample, residuals, mmfs_features, mmfs_mask)``.
     The results live in buffers owned by the graph and are overwritten by the next replay.
-    Inference only (no autograd through a replay)."""
+    Inference only (no autograd through a replay).  With ``net.kept_bank_dtype`` = torch.float8_e4m3fn the projections
+    are fp8 banks: the graph holds them and their scales (``ProjectedFeatures.scales``)."""
 
     def __init__(self, net, sample, down_block_res_samples, mmfs_features, mmfs_mask, warmup=2, bank_repeat=None):
         # (``bank_repeat``: as ``MMFSNet.forward`` -- the features are a bank shared by the rows of ``sample``)
@@ -52,7 +53,7 @@ class GraphedMMFSNet:
         self.net = net
         with torch.no_grad():
             proj = mmfs_features if isinstance(mmfs_features, ProjectedFeatures) \
-                else net.project_features(mmfs_features)
+                else net.project_features(mmfs_features, bank_dtype=net.kept_bank_dtype)
             self._proj, self._mask = proj, mmfs_mask.clone()
             self._sample = sample.clone()
             self._res = [r.clone() for r in down_block_res_samples]
@@ -91,16 +92,22 @@ class GraphedLlamaMMFSStack:
     ``g(hidden)`` replays it.  The dense LLaMA layers that sit between the MMFS layers in the real decoder are out
     of scope here (a caller that graphs its whole decode step captures these layers with the rest: the op and the
     modules are capture-safe as they are -- no device->host copy, current stream, allocator workspaces).
-    Inference only; the result lives in a buffer owned by the graph."""
+    Inference only; the result lives in a buffer owned by the graph.  ``kept_bank_dtype`` (torch.float8_e4m3fn, or None:
+    ``LlamaMMFSSchedule.kept_bank_dtype``): the projections as fp8 banks, held by the graph with their scales."""
 
-    def __init__(self, layers, hidden, vision_hidden_states, cross_attention_mask, warmup=2):
+    def __init__(self, layers, hidden, vision_hidden_states, cross_attention_mask, warmup=2, kept_bank_dtype=None):
         assert hidden.is_cuda
         self.layers = list(layers)
         assert not any(l.training for l in self.layers), \
             "GraphedLlamaMMFSStack is inference only: layer.eval() first (nothing is folded or kept in training mode)"
         with torch.no_grad():
-            bank = vision_hidden_states if isinstance(vision_hidden_states, ProjectedBank) \
-                else LlamaMMFSSchedule(self.layers).project(vision_hidden_states)
+            if isinstance(vision_hidden_states, ProjectedBank):
+                bank = vision_hidden_states
+            else:
+                schedule = LlamaMMFSSchedule(self.layers)
+                if kept_bank_dtype is not None:
+                    schedule.kept_bank_dtype = kept_bank_dtype
+                bank = schedule.project(vision_hidden_states)
             self._bank, self._mask = bank, cross_attention_mask.clone()
             self._hidden = hidden.clone()
             # (the mask is fixed for the life of the graph: the images' ranks are made here, once, not in it)
@@ -121,7 +128,11 @@ class GraphedLlamaMMFSStack:
     def _run(self):
         h = self._hidden
         for k, layer in enumerate(self.layers):
-            h = layer(h, self._bank.bank, self._mask, value=self._bank.values[k], image_ranks=self._ranks, residual=h)
+            # (a shared bank serves its rows in the ProjectedBank's order; an fp8 bank comes with its scales)
+            kw = {} if self._bank.bank_repeat is None else dict(bank_repeat=self._bank.bank_repeat)
+            if self._bank.scales is not None:
+                kw["value_scale"] = self._bank.scales[k]
+            h = layer(h, self._bank.bank, self._mask, value=self._bank.values[k], image_ranks=self._ranks, residual=h, **kw)
         return h
 
     @torch.no_grad()

@@ -278,7 +278,8 @@ class MMFS(CacheInvalidation, nn.Module):
                 # returns the op's output and the sink weights instead of loc / attn
                 # (``sampler[2]``: the ignore token, whose term the kernel then adds itself -- the sink weights come back None)
                 res = mmfs_sample_forward(sampler[0], input_spatial_shapes, sampler[1], *heads[:4], relpos,
-                                          heads[5], self._ratios32(), H, L, P, token=sampler[2], value_repeat=bank_repeat)
+                                          heads[5], self._ratios32(), H, L, P, token=sampler[2], value_repeat=bank_repeat,
+                                          value_scale=sampler[3])
                 if res is not None:
                     return None, res[0], (res[1] if sampler[2] is None else None)
             loc, attn, sink_sum = MMFSPlanFunction.apply(off_q.contiguous(), att_q.contiguous(), *heads[2:])
@@ -353,7 +354,7 @@ class MMFS(CacheInvalidation, nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
                 input_level_start_index, input_padding_mask=None, attention_mask=None, value=None, image_ranks=None,
-                output_weights=None, output_residual=None, output_gate=None, bank_repeat=None):
+                output_weights=None, output_residual=None, output_gate=None, bank_repeat=None, value_scale=None):
         """Arguments and result as mmfs.py:120-141 (``value`` is an addition: the caller's own
         ``value_proj(input_flatten)`` [N, n, hw, d_inner], e.g. one an ``MMFSNet`` projected for
         all its blocks at once; ``input_flatten`` is then only looked at for its shape; ``image_ranks`` another: this
@@ -371,7 +372,10 @@ class MMFS(CacheInvalidation, nn.Module):
         guidance's ``torch.cat([features] * 2)``, beam search's ``repeat_interleave(num_beams, 0)``: ``input_flatten`` /
         ``value`` / ``input_padding_mask`` then have the bank's batch Nv and ``query``, ``reference_points`` (when batched)
         and ``attention_mask`` the query batch N = g * Nv; query row b reads bank row b % Nv ("tile") or b // g
-        ("interleave").  The value projection runs on the Nv rows; the result is the module's on the expanded bank."""
+        ("interleave").  The value projection runs on the Nv rows; the result is the module's on the expanded bank.
+        ``value_scale`` (a seventh): with ``value`` an fp8 bank (``MultiScaleDeformableAttention.quantize_bank_fp8`` of the
+        projection viewed as [Nb, n*hw, 1, d_inner]), its fp32 scales [Nb, d_inner] -- inference only; the output keeps
+        ``query``'s type."""
         N, Lq, _ = query.shape
         if bank_repeat is None:
             N, n, hw, _ = input_flatten.shape
@@ -390,19 +394,26 @@ class MMFS(CacheInvalidation, nn.Module):
             value = self.value_proj(input_flatten)
         else:
             assert value.shape == (Nb, n, hw, self.d_inner), (value.shape, (Nb, n, hw, self.d_inner))
+        fp8 = value_scale is not None
+        if fp8:
+            assert value.dtype == torch.float8_e4m3fn and value_scale.shape == (Nb, self.d_inner), (value.dtype, value_scale.shape)
         if input_padding_mask is not None:
-            value = value.masked_fill(input_padding_mask[..., None], 0.0)
+            if fp8:                               # (e4m3 0x00 is +0)
+                value = value.view(torch.uint8).masked_fill(input_padding_mask[..., None], 0).view(torch.float8_e4m3fn)
+            else:
+                value = value.masked_fill(input_padding_mask[..., None], 0.0)
         value = value.reshape(Nb, n * hw, self.n_heads, self.d_inner // self.n_heads).contiguous()
 
         # no autograd graph wanted (sampling / decoding): plan and sampler run as one kernel, the locations
         # and weights never exist as tensors (csrc/mmfs_plan.hip, mmfs_sample_fwd); bit-identical output
-        fuse = (self.fused_sampler and self.fused_plan and value.is_cuda and query.dtype == value.dtype
+        fuse = (self.fused_sampler and self.fused_plan and value.is_cuda and (query.dtype == value.dtype or fp8)
                 and not (torch.is_grad_enabled() and (query.requires_grad or value.requires_grad
                                                       or any(p.requires_grad for p in self.parameters()))))
         # (the ignore token's term inside the fused kernel where the types agree: else three framework kernels below)
-        tok_in = self.ignore_token if (fuse and self.ignore_token.dtype == value.dtype) else None
+        out_dtype = query.dtype if fp8 else value.dtype
+        tok_in = self.ignore_token if (fuse and self.ignore_token.dtype == out_dtype) else None
         loc, attn, sink_w = self.sampling_plan(query, reference_points, input_spatial_shapes, attention_mask, n,
-                                               sampler=(value, input_level_start_index, tok_in) if fuse else None,
+                                               sampler=(value, input_level_start_index, tok_in, value_scale) if fuse else None,
                                                image_ranks=image_ranks, bank_repeat=bank_repeat)
         if loc is None:
             out = attn                            # (the fused kernel's result)
@@ -412,9 +423,14 @@ class MMFS(CacheInvalidation, nn.Module):
             # (last argument: the softmax that made ``attn`` multiplies the gradient of every weight by the
             # weight itself, so the op need not compute it where the weight -- an invisible image -- is 0)
             # (the map only when there is one: the op's unshared call keeps its argument list)
-            out = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
-                                             loc.to(value.dtype).contiguous(), attn, self.im2col_step, True,
-                                             *((bank_repeat,) if bank_repeat is not None else ()))
+            if fp8:
+                out = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
+                                                 loc.to(attn.dtype).contiguous(), attn, self.im2col_step, True, bank_repeat,
+                                                 value_scale.contiguous())
+            else:
+                out = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
+                                                 loc.to(value.dtype).contiguous(), attn, self.im2col_step, True,
+                                                 *((bank_repeat,) if bank_repeat is not None else ()))
         # the sinks' share goes to the (frozen, zero-initialised) ignore token (mmfs.py:236-241, 274)
         tok = self.ignore_token.view(1, 1, self.n_heads, -1)
         if (out.is_cuda and torch.is_grad_enabled() and not torch.is_autocast_enabled() and tok.dtype == out.dtype
