@@ -586,6 +586,14 @@ def _seed_level_info(spatial_shapes, key, sh, st, S):
     return info
 
 
+def host_level_counts(host_shapes):
+    """(4x4 pixel blocks of all levels, levels with pixels) of a host level table [L, 2]: what the sorted and hybrid
+    backwards are told.  A level of H * W == 0 has neither (it owns no pixel and no sort tile)."""
+    hs = np.asarray(host_shapes, dtype=np.int64).reshape(-1, 2)
+    live = (hs[:, 0] > 0) & (hs[:, 1] > 0)
+    return int((((hs[:, 0] + 3) // 4) * ((hs[:, 1] + 3) // 4))[live].sum()), int(live.sum())
+
+
 def register_level_tables(spatial_shapes, level_start_index, S, host_shapes=None, host_start=None):
     """Tell the shim what a pair of device level tables contains (one device->host copy now, or
     none when the host copies are passed), so that neither pass ever has to look: enables the
@@ -677,8 +685,7 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         if srt_bytes > 0:
             route_counts["sorted"] += 1
             ws = torch.empty(srt_bytes, dtype=torch.uint8, device=value.device)
-            hs = info[1]
-            blocks4 = int((((hs[:, 0] + 3) // 4) * ((hs[:, 1] + 3) // 4))[(hs[:, 0] > 0) & (hs[:, 1] > 0)].sum())
+            blocks4 = host_level_counts(info[1])[0]
             sargs = (code, value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
                      sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
                      grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), ws.data_ptr(), srt_bytes,
@@ -717,7 +724,7 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
             fused = _ws_cache.get(fkey)
             if fused is None:
                 fused = _ws_cache[fkey] = _lib.mmfs_msda_backward_taps_fused(code, *dims, flags)
-            sorted_levels = int(((info[1][:, 0] > 0) & (info[1][:, 1] > 0)).sum())
+            sorted_levels = host_level_counts(info[1])[1]
 
             def run_stages(stages):
                 st = 0

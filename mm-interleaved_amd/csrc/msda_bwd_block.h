@@ -77,7 +77,8 @@ struct CellHeader {
     int n_tiles, n_blocks, n_cells, L;
     int n_blocks4, pad[3];              // 4x4 blocks of all levels (matrix-core reduce); pad[0]: every row has exactly one owner level;
                                         // pad[1]: levels cut into more than one sort tile (their seams' blocks are planned by the slice's last workgroup)
-    uint32_t stamp, reserved;           // what the plan was made for (header_stamp): a sort / reduce handed another call's workspace finds nothing to do
+    uint32_t stamp;                     // what the plan was made for (header_stamp): a sort / reduce handed another call's workspace finds nothing to do
+    uint32_t n_empty;                   // levels of H * W == 0 (no tiles: Dims::taps_sorted zeroes their samples' gradients in tile 0's workgroup)
     const void *loc_src, *attn_src;     // the op's own loc / attn when the sort reads them in place (no re-pack), else null
 };
 

@@ -444,6 +444,24 @@ msda_bwd_cell_sort(const T *loc, const T *attn, uint4 *__restrict__ records,
         t = within / tp.hgroup;
     }
     if (hdr->stamp != header_stamp(d) || t >= hdr->n_tiles) return;      // (a plan made for other dimensions: not ours)
+    // Dims::taps_sorted: a level of H * W == 0 has no tile, so no first tile writes the zero gradients of its samples (none
+    // of them gets a record): the (b, h) slice's tile 0 does, for every such level.  A table without one: a header word.
+    // (Behind the n_tiles test above: a plan of no tiles writes no zeros.  It cannot reach here -- S > 0 means some level
+    // has pixels, hence a tile, and mmfs_msda_backward_sorted refuses S == 0.)
+    if (TS && t == 0 && ta.g_loc != nullptr && hdr->n_empty != 0u) {
+        const LevelRow *lv = level_rows(hdr);
+        T *g_loc = reinterpret_cast<T *>(ta.g_loc), *g_attn = reinterpret_cast<T *>(ta.g_attn);
+        const int64_t per_level = (int64_t)d.Nq * d.P;
+        for (int l = 0; l < d.L; ++l) {
+            if (lv[l].Hl != 0 && lv[l].Wl != 0) continue;
+            for (int64_t i = threadIdx.x; i < per_level; i += THREADS) {
+                const int64_t q = i / d.P, p = i - q * d.P;
+                const int64_t s = ((((int64_t)b * d.Nq + q) * d.H + h) * d.L + l) * d.P + p;
+                g_attn[s] = (T)0.f;
+                g_loc[2 * s] = (T)0.f; g_loc[2 * s + 1] = (T)0.f;
+            }
+        }
+    }
     const CTile tl = tiles_of(hdr, d.L)[t];
     // (matrix-core reduce: the level's row, for the blocks this tile plans itself; asked for early)
     LevelRow lr = {};

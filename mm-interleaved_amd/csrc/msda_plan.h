@@ -102,12 +102,13 @@ __device__ inline void plan_cells_body(const PlanArgs &pa, unsigned char *lds)
     }
     __syncthreads();
     if (tid == 0) {
-        int cbase = 0, bbase = 0, bbase4 = 0, seamed = 0;
+        int cbase = 0, bbase = 0, bbase4 = 0, seamed = 0, empty = 0;
         int64_t covered = 0, n = 0;
         for (int l = 0; l < L; ++l) {
             LevelRow &r = rows[l];
             r.cbase = cbase; r.bbase = bbase; r.bbase4 = bbase4;
             tile_base[l] = (int)min(n, (int64_t)cap);
+            if (r.Hl == 0 || r.Wl == 0) ++empty;
             if (tile_n[l] == 0) continue;                                // (empty, or refused below)
             bbase4 += r.nbx4 * r.nby4;
             n += tile_n[l];
@@ -119,7 +120,7 @@ __device__ inline void plan_cells_body(const PlanArgs &pa, unsigned char *lds)
         }
         hdr->n_tiles = (int)min(n, (int64_t)cap); hdr->n_blocks = bbase; hdr->n_cells = cbase; hdr->L = L;
         hdr->n_blocks4 = bbase4; hdr->pad[1] = seamed; hdr->pad[2] = 0;
-        hdr->stamp = pa.stamp; hdr->reserved = 0u;
+        hdr->stamp = pa.stamp; hdr->n_empty = (uint32_t)empty;
         hdr->loc_src = pa.loc_src; hdr->attn_src = pa.attn_src;
         covered_all = covered == (int64_t)S;
     }

@@ -52,6 +52,12 @@ def one_case(rng, idx):
             dtype = torch.bfloat16
     elif B * Nq * H * L * P * D > 6e7:
         Nq = 33 if P < 32 else 130
+    # degenerate levels, from a stream of their own (every seed keeps the cases it had unless this draw fires): one level
+    # empty -- (0, W), (H, 0) or (0, 0): no pixels, no sort tile, its samples' gradients exactly 0
+    deg = random.Random(idx * 7919 + 17)
+    if deg.random() < 0.1 and L > 1:
+        lvl = deg.randrange(L)
+        shapes[lvl] = deg.choice([(0, shapes[lvl][1]), (shapes[lvl][0], 0), (0, 0)])
     g = torch.Generator().manual_seed(idx)
     sh = torch.tensor(shapes, dtype=torch.long)
     st = torch.cat((sh.new_zeros(1), sh.prod(1).cumsum(0)[:-1]))

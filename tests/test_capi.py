@@ -138,6 +138,26 @@ def test_canonical_level_table_detection_and_cache():
     assert not MSDA.levels_are_canonical(sh, st, 20)
 
 
+def test_empty_levels_are_canonical_and_own_no_blocks():
+    """A level of H * W == 0 is canonical wherever it sits (its start index repeats the next level's, or equals S when
+    it is last) and adds nothing to the 4x4 blocks / levels with pixels the sorted and hybrid backwards are told."""
+    import MultiScaleDeformableAttention as MSDA
+    cases = [  # shapes, start, S, blocks4, levels with pixels
+        ([[0, 5], [4, 4], [2, 2]], [0, 0, 16], 20, 1 + 1, 2),
+        ([[4, 4], [3, 0], [0, 0], [2, 2]], [0, 16, 16, 16], 20, 1 + 1, 2),
+        ([[4, 4], [2, 2], [0, 0]], [0, 16, 20], 20, 1 + 1, 2),
+        ([[5, 9], [0, 7]], [0, 45], 45, 2 * 3, 1),
+        ([[0, 3], [0, 0]], [0, 0], 0, 0, 0),
+    ]
+    for shapes, start, S, blocks4, live in cases:
+        sh, st = torch.tensor(shapes), torch.tensor(start)
+        assert MSDA.levels_are_canonical(sh, st, S), shapes
+        assert MSDA.host_level_counts(sh.numpy()) == (blocks4, live), shapes
+    # an empty level does not make a wrong start index right
+    assert not MSDA.levels_are_canonical(torch.tensor([[4, 4], [0, 3], [2, 2]]), torch.tensor([0, 16, 17]), 20)
+    assert not MSDA.levels_are_canonical(torch.tensor([[4, 4], [0, 3], [2, 2]]), torch.tensor([0, 15, 16]), 20)
+
+
 def test_hybrid_workspace_queries_are_host_only():
     """mmfs_msda_backward_hybrid routes grad_loc / grad_attn of levels of <= 256 pixels to the matrix
     cores when the caller hands over a HOST copy of the level table; its workspace query computes on

@@ -218,3 +218,32 @@ def test_rejects_a_dropped_bilinear_corner_in_out(dtype):
         res = Hp.bound_ratios(rounded(got, dtype), x, dtype, outputs=("out",), bounds=bounds)
         rejected += res["out"][0] > 1.0
     assert rejected == 6
+
+
+def test_poisoned_allocation_of_an_unwritten_output_breaks_the_bound(monkeypatch):
+    """helpers.poison_allocations: under it, an output nobody writes fails assert_within_bounds -- the caching allocator
+    can no longer hand a kernel that skips elements the block holding the previous identical call's answer.  The one
+    level with H * W == 0 is where that bites: its samples' gradients must be written as exact zeros."""
+    x = make_inputs(1, 2, 8, 5, 4, [(4, 4), (0, 3), (2, 2)], seed=2, loc_range=(-0.1, 1.1), dtype=torch.bfloat16)
+    ref = [np.asarray(r) for r in Hp._oracle(x)]
+    Hp.assert_within_bounds(ref, x, torch.bfloat16, "oracle")
+    Hp.poison_allocations(monkeypatch)
+    for k, name in enumerate(Hp.OUTPUTS):
+        got = list(ref)
+        got[k] = torch.empty(np.asarray(ref[k]).shape, dtype=torch.bfloat16).double().numpy()     # never written
+        assert np.isnan(got[k]).all()
+        with pytest.raises(AssertionError, match=name):
+            Hp.assert_within_bounds(got, x, torch.bfloat16, "unwritten")
+    # only the empty level's grad_loc / grad_attn left unwritten (what the sorted backward did): caught too
+    for k in (2, 3):
+        got = list(ref)
+        part = torch.from_numpy(np.asarray(ref[k]).copy()).reshape(x["loc"].shape[:5] + ((2,) if k == 2 else ()))
+        part[:, :, :, 1] = torch.empty_like(part[:, :, :, 1])
+        got[k] = part.numpy()
+        with pytest.raises(AssertionError, match="level=1"):
+            Hp.assert_within_bounds(got, x, torch.bfloat16, "empty level unwritten")
+    # the other types: uint8 workspaces 0xA5, integers a non-zero pattern, bool True
+    assert (torch.empty(7, dtype=torch.uint8) == 0xA5).all()
+    assert (torch.empty_like(torch.zeros(3, dtype=torch.int32)) == 0x5A5A5A5A).all()
+    assert (torch.empty(2, 2, dtype=torch.int64) != 0).all() and torch.empty(3, dtype=torch.bool).all()
+    assert torch.isnan(torch.empty(4, requires_grad=True)).all()

@@ -105,6 +105,28 @@ def test_kernel_edge_semantics():
     assert 0.0 < out < 1e-3 and gl.reshape(-1)[0] < 0    # moving right loses the last column
 
 
+@pytest.mark.parametrize("empty,at", [((0, 5), 0), ((4, 0), 1), ((0, 0), 2), ((0, 3), 3)])
+def test_empty_level_is_the_table_without_it(empty, at):
+    """A level with H * W == 0 (first, in the middle, last: its start index == S) owns no pixel: the forward and
+    grad_value are those of the table without it, exactly, and its samples' grad_loc / grad_attn are exactly 0."""
+    full = [(5, 4), (3, 6), (2, 2)]
+    shapes = full[:at] + [empty] + full[at:]
+    x = make_inputs(B=2, H=2, D=5, Nq=6, P=3, shapes=shapes, seed=at, loc_range=(-0.2, 1.2), dtype=torch.float64)
+    sh, start = level_tables(shapes)
+    keep = [l for l in range(len(shapes)) if l != at]
+    sh0, start0 = level_tables(full)
+    loc0, attn0 = x["loc"][:, :, :, keep].contiguous(), x["attn"][:, :, :, keep].contiguous()
+    out = msda_oracle.forward(x["value"], sh, start, x["loc"], x["attn"])
+    gv, gl, ga = msda_oracle.backward(x["value"], sh, start, x["loc"], x["attn"], x["grad"])
+    out0 = msda_oracle.forward(x["value"], sh0, start0, loc0, attn0)
+    gv0, gl0, ga0 = msda_oracle.backward(x["value"], sh0, start0, loc0, attn0, x["grad"])
+    assert np.array_equal(out, out0) and np.array_equal(gv, gv0)
+    gl, ga = np.asarray(gl).reshape(x["loc"].shape), np.asarray(ga).reshape(x["attn"].shape)
+    assert not gl[:, :, :, at].any() and not ga[:, :, :, at].any()
+    assert np.array_equal(gl[:, :, :, keep], np.asarray(gl0).reshape(loc0.shape))
+    assert np.array_equal(ga[:, :, :, keep], np.asarray(ga0).reshape(attn0.shape))
+
+
 def test_empty_and_ragged_shapes():
     sh, start = level_tables([(3, 1), (1, 5)])
     v = np.random.default_rng(0).random((2, 8, 2, 4))
