@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_bank_quantize_fp8, mmfs_msda_forward_fp8, mmfs_sample_forward_heads_fp8:
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_deform_plan_supported / _forward / _backward, mmfs_deform_sample_forward: the image
+                                   *     encoder's MSDeformAttn front end, see "The image encoder's MSDeformAttn" below
+                                   * 14 (additive): + mmfs_bank_quantize_fp8, mmfs_msda_forward_fp8, mmfs_sample_forward_heads_fp8:
                                    *     the inference-only fp8 (e4m3) value bank with fp32 scales, see "fp8 bank" below
                                    * 14: + mmfs_msda_forward_shared, mmfs_sample_forward_heads_shared: one value bank of Bv rows serves
                                    *     B = g * Bv query rows (MMFS_BANK_TILE / MMFS_BANK_INTERLEAVE) without being copied
@@ -549,6 +551,48 @@ int mmfs_sample_forward_heads_fp8(int dtype, const void *q, const float *scale, 
  * a query is requested at once and the groups' fp32 partial sums are added in a fixed tree: the same products, equal to
  * the two calls within one rounding of the storage type, deterministic.  0 for shapes mmfs_sample_forward refuses. */
 int mmfs_sample_forward_groups(int dtype, int64_t Lq, int64_t D, int64_t nL, int64_t P);
+
+/* ---------------------------------------------------------------------------------------------
+ * The image encoder's MSDeformAttn (ViT-Adapter): its sampling plan (csrc/msda_deform_plan.hip; additive at ABI 14).
+ * Replaces what mm_interleaved/models/encoders/vit_adapter/ops/modules/ms_deform_attn.py:108-127 runs between its two
+ * Linear heads and the op -- softmax, division by the level extent, add of the reference point, cast, two copies:
+ *   off    [N, Lq, H, L, P, 2]  sampling_offsets(query)       storage type ``dtype`` (MMFS_F32 / MMFS_F16 / MMFS_BF16);
+ *   logit  [N, Lq, H, L, P]     attention_weights(query)      token rows ``ld_off`` / ``ld_att`` ELEMENTS apart (0 = packed,
+ *                                                             H*L*P*2 / H*L*P): both may be column ranges of one GEMM result
+ *   ref    [Nr, Lq, Lref, R]    fp32; Nr = 1 or N, Lref = 1 or L (broadcast over the batch / the levels), R = 2 or 4
+ *   shapes [L, 2]               int64 (H_l, W_l), device memory
+ *   attn = softmax of the L*P logits of (n, q, h);   R = 2: loc = ref + off / (W_l, H_l);
+ *   R = 4: loc = ref[:2] + off / P * ref[2:] * 0.5.   fp32 arithmetic, ONE rounding to the storage type at the store.
+ * mmfs_deform_plan_forward  -> loc [N, Lq, H, L, P, 2], attn [N, Lq, H, L, P] (packed, 16-byte aligned), every element written.
+ * mmfs_deform_plan_backward -> grad_off / grad_logit in the storage type, written with the forward's leading dimensions (one
+ *   stacked gradient tensor feeds one GEMM backward): grad_logit_i = a_i (g_i - sum_j a_j g_j) from the saved ``attn``;
+ *   grad_off = grad_loc * (1/W_l, 1/H_l) (R = 2) or * ref[2:] * 0.5 / P (R = 4).  Every element has one writer: no atomics,
+ *   nothing to clear.  There is no gradient for ``ref``.
+ * mmfs_deform_sample_forward: the plan feeding mmfs_msda_forward's row gather in ONE kernel, for calls without gradients --
+ *   loc / attn never reach memory.  They are rounded to the storage type inside the kernel before use, with the plan kernel's
+ *   own arithmetic and reduction order: ``out`` [N, Lq, H*D] is a function of the same numbers the two calls see.  value
+ *   [N, S, H, D] and out 16-byte aligned.  MMFS_E_UNSUPPORTED (run the two calls) unless D * sizeof(T) is 32 .. 512 bytes,
+ *   a power of two, and a value slab is below 2 GiB.
+ * mmfs_deform_plan_supported: bit 0 = the plan kernels serve (dtype, L, P, R): P in {2, 4, 8}, L <= 8; bit 1 = the fused
+ *   sampler serves head rows of D elements as well (D = 0 asks about the plan only).  Host only.
+ * Errors come back before any launch: MMFS_E_DTYPE; MMFS_E_DIMS for a negative dimension, Nr / Lref / R outside the sets above
+ * or a leading dimension below the packed one; MMFS_E_UNSUPPORTED for P / L / D outside the kernels' range; MMFS_E_NULLPTR
+ * for a NULL tensor of a non-empty problem; MMFS_E_ALIGN for rows the vector accesses cannot take.  N * Lq == 0 returns 0. */
+int mmfs_deform_plan_supported(int dtype, int64_t L, int64_t P, int64_t R, int64_t D);
+int mmfs_deform_plan_forward(int dtype, const void *off, const void *logit, int64_t ld_off, int64_t ld_att,
+                             const float *ref, const int64_t *shapes, void *loc, void *attn,
+                             int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P, int64_t Nr, int64_t Lref, int64_t R,
+                             void *stream);
+int mmfs_deform_plan_backward(int dtype, const void *grad_loc, const void *grad_attn, const void *attn,
+                              const float *ref, const int64_t *shapes, void *grad_off, void *grad_logit,
+                              int64_t ld_off, int64_t ld_att,
+                              int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P, int64_t Nr, int64_t Lref, int64_t R,
+                              void *stream);
+int mmfs_deform_sample_forward(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
+                               const void *off, const void *logit, int64_t ld_off, int64_t ld_att,
+                               const float *ref, void *out,
+                               int64_t N, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L, int64_t P,
+                               int64_t Nr, int64_t Lref, int64_t R, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

@@ -1,0 +1,221 @@
+"""The ViT-Adapter's interaction blocks -- the image encoder's callers of ``MSDeformAttn``
+(mm_interleaved/models/encoders/vit_adapter/adapter_modules.py:15-233; 4 interaction blocks = 4 injectors +
+6 extractors per ViT forward).  Constructor signatures and ``state_dict`` keys are the reference's, so its
+checkpoints load with ``strict=True``; the ``attn`` of every block takes the fused front end
+(``MSDeformAttn.fused_front_end``, csrc/msda_deform_plan.hip).  LayerNorm, the Linear layers, GELU and the
+depthwise convolution are framework ops.
+
+Differences from the reference, none of them in the numbers:
+  * ``deform_inputs`` / ``get_reference_points`` build their tensors once per (image size, device) -- the level
+    tables through ``levels.make_level_tables``, which also marks them as canonically packed for the op's backward --
+    instead of six tensors per call;
+  * stochastic depth is a module of this file (no ``timm`` import).
+"""
+from functools import partial
+
+import torch
+import torch.nn as nn
+import torch.utils.checkpoint as cp
+
+from ..levels import make_level_tables
+from ..modules import MSDeformAttn
+
+_ref_cache = {}
+_inputs_cache = {}
+
+
+def get_reference_points(spatial_shapes, device):
+    """Pixel centres of the maps ``spatial_shapes`` [(H, W), ...], normalised to [0, 1], as (x, y):
+    [1, sum H*W, 1, 2] fp32 -- one reference point per query, shared by the batch and by the levels.  Kept per
+    (shapes, device)."""
+    key = (tuple((int(h), int(w)) for h, w in spatial_shapes), str(torch.device(device)))
+    hit = _ref_cache.get(key)
+    if hit is not None:
+        return hit
+    # (kept tensors: built outside inference mode, see levels.make_level_tables)
+    with torch.inference_mode(False), torch.no_grad():
+        maps = []
+        for h, w in key[0]:
+            ys = torch.linspace(0.5, h - 0.5, h, dtype=torch.float32, device=device) / h
+            xs = torch.linspace(0.5, w - 0.5, w, dtype=torch.float32, device=device) / w
+            maps.append(torch.stack((xs[None, :].expand(h, w), ys[:, None].expand(h, w)), -1).reshape(1, h * w, 2))
+        points = torch.cat(maps, 1)[:, :, None].contiguous()
+    _ref_cache[key] = points
+    return points
+
+
+def deform_inputs(x):
+    """x [B, C, h, w] (the image) -> ([reference_points, spatial_shapes, level_start_index] of the injector: the ViT's
+    stride-16 tokens query the stride-8 / 16 / 32 pyramid;  the same three of the extractor: the pyramid's tokens query
+    the stride-16 map).  The same tensor objects for every image of one size on one device."""
+    h, w = int(x.shape[2]), int(x.shape[3])
+    key = (h, w, str(x.device))
+    hit = _inputs_cache.get(key)
+    if hit is not None:
+        return hit
+    pyramid = [(h // 8, w // 8), (h // 16, w // 16), (h // 32, w // 32)]
+    vit = [(h // 16, w // 16)]
+    shapes1, start1, _ = make_level_tables(pyramid, 1, x.device)
+    shapes2, start2, _ = make_level_tables(vit, 1, x.device)
+    out = ([get_reference_points(vit, x.device), shapes1, start1],
+           [get_reference_points(pyramid, x.device), shapes2, start2])
+    _inputs_cache[key] = out
+    return out
+
+
+class DropPath(nn.Module):
+    """Stochastic depth: in training a sample's residual branch is dropped with probability ``drop_prob`` and the
+    kept ones are scaled by 1 / (1 - drop_prob); the identity in eval mode."""
+
+    def __init__(self, drop_prob=0.0):
+        super().__init__()
+        self.drop_prob = float(drop_prob)
+
+    def forward(self, x):
+        if self.drop_prob == 0.0 or not self.training:
+            return x
+        keep = 1.0 - self.drop_prob
+        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        if keep > 0.0:
+            mask.div_(keep)
+        return x * mask
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob:.3f}"
+
+
+class DWConv(nn.Module):
+    """Depthwise 3x3 convolution of the pyramid's tokens: the 21 n tokens are the stride-8 map (16 n = 2H x 2W), the
+    stride-16 map (4 n = H x W) and the stride-32 map (n), each convolved as an image with the same weights."""
+
+    def __init__(self, dim=768):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, 3, 1, 1, bias=True, groups=dim)
+
+    def forward(self, x, H, W):
+        B, N, C = x.shape
+        n = N // 21
+        parts = []
+        for lo, hi, (hh, ww) in ((0, 16 * n, (H * 2, W * 2)), (16 * n, 20 * n, (H, W)), (20 * n, N, (H // 2, W // 2))):
+            img = x[:, lo:hi].transpose(1, 2).reshape(B, C, hh, ww)
+            parts.append(self.dwconv(img).flatten(2).transpose(1, 2))
+        return torch.cat(parts, 1)
+
+
+class ConvFFN(nn.Module):
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.dwconv = DWConv(hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x, H, W):
+        x = self.drop(self.act(self.dwconv(self.fc1(x), H, W)))
+        return self.drop(self.fc2(x))
+
+
+def _adapter_attn(dim, n_levels, num_heads, n_points, deform_ratio):
+    attn = MSDeformAttn(d_model=dim, n_levels=n_levels, n_heads=num_heads, n_points=n_points, ratio=deform_ratio)
+    attn.fused_front_end = True
+    return attn
+
+
+def _maybe_checkpoint(with_cp, fn, query, feat):
+    if with_cp and query.requires_grad:
+        return cp.checkpoint(fn, query, feat, use_reentrant=False)
+    return fn(query, feat)
+
+
+class Extractor(nn.Module):
+    """Pyramid tokens (``query``) read the ViT's map (``feat``): query + attn, then the convolutional FFN."""
+
+    def __init__(self, dim, num_heads=6, n_points=4, n_levels=1, deform_ratio=1.0, with_cffn=True, cffn_ratio=0.25,
+                 drop=0., drop_path=0., norm_layer=partial(nn.LayerNorm, eps=1e-6), with_cp=False):
+        super().__init__()
+        self.query_norm = norm_layer(dim)
+        self.feat_norm = norm_layer(dim)
+        self.attn = _adapter_attn(dim, n_levels, num_heads, n_points, deform_ratio)
+        self.with_cffn = with_cffn
+        self.with_cp = with_cp
+        if with_cffn:
+            self.ffn = ConvFFN(in_features=dim, hidden_features=int(dim * cffn_ratio), drop=drop)
+            self.ffn_norm = norm_layer(dim)
+            self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+
+    def forward(self, query, reference_points, feat, spatial_shapes, level_start_index, H, W):
+        def inner(query, feat):
+            query = query + self.attn(self.query_norm(query), reference_points, self.feat_norm(feat), spatial_shapes,
+                                      level_start_index, None)
+            if self.with_cffn:
+                query = query + self.drop_path(self.ffn(self.ffn_norm(query), H, W))
+            return query
+
+        return _maybe_checkpoint(self.with_cp, inner, query, feat)
+
+
+class Injector(nn.Module):
+    """ViT tokens (``query``) read the pyramid (``feat``): query + gamma * attn."""
+
+    def __init__(self, dim, num_heads=6, n_points=4, n_levels=1, deform_ratio=1.0,
+                 norm_layer=partial(nn.LayerNorm, eps=1e-6), init_values=0., with_cp=False):
+        super().__init__()
+        self.with_cp = with_cp
+        self.query_norm = norm_layer(dim)
+        self.feat_norm = norm_layer(dim)
+        self.attn = _adapter_attn(dim, n_levels, num_heads, n_points, deform_ratio)
+        self.gamma = nn.Parameter(init_values * torch.ones(dim), requires_grad=True)
+
+    def forward(self, query, reference_points, feat, spatial_shapes, level_start_index):
+        def inner(query, feat):
+            return query + self.gamma * self.attn(self.query_norm(query), reference_points, self.feat_norm(feat),
+                                                  spatial_shapes, level_start_index, None)
+
+        return _maybe_checkpoint(self.with_cp, inner, query, feat)
+
+
+class InteractionBlock(nn.Module):
+    """Injector -> the ViT's own layers (``blocks``: modules called as ``blk(x, H, W)``) -> extractor(s)."""
+
+    def __init__(self, dim, num_heads=6, n_points=4, norm_layer=partial(nn.LayerNorm, eps=1e-6), drop=0., drop_path=0.,
+                 with_cffn=True, cffn_ratio=0.25, init_values=0., deform_ratio=1.0, extra_extractor=False,
+                 with_cp=False):
+        super().__init__()
+        self.injector = Injector(dim=dim, n_levels=3, num_heads=num_heads, init_values=init_values, n_points=n_points,
+                                 norm_layer=norm_layer, deform_ratio=deform_ratio, with_cp=with_cp)
+        ext = partial(Extractor, dim=dim, num_heads=num_heads, n_points=n_points, norm_layer=norm_layer,
+                      deform_ratio=deform_ratio, with_cffn=with_cffn, cffn_ratio=cffn_ratio, drop=drop,
+                      drop_path=drop_path, with_cp=with_cp)
+        self.extractor = ext(n_levels=1)
+        self.extra_extractors = nn.Sequential(ext(), ext()) if extra_extractor else None
+
+    def _inject(self, x, c, deform_inputs1):
+        return self.injector(query=x, reference_points=deform_inputs1[0], feat=c, spatial_shapes=deform_inputs1[1],
+                             level_start_index=deform_inputs1[2])
+
+    def _extract(self, x, c, deform_inputs2, H, W):
+        extractors = [self.extractor] + (list(self.extra_extractors) if self.extra_extractors is not None else [])
+        for e in extractors:
+            c = e(query=c, reference_points=deform_inputs2[0], feat=x, spatial_shapes=deform_inputs2[1],
+                  level_start_index=deform_inputs2[2], H=H, W=W)
+        return c
+
+    def forward(self, x, c, blocks, deform_inputs1, deform_inputs2, H, W):
+        x = self._inject(x, c, deform_inputs1)
+        for blk in blocks:
+            x = blk(x, H, W)
+        return x, self._extract(x, c, deform_inputs2, H, W)
+
+
+class InteractionBlockWithCls(InteractionBlock):
+    """The same around a ViT with a class token: ``blocks`` is any callable on [cls | tokens] whose result has
+    ``.last_hidden_state`` (the CLIP encoder's layers in the reference)."""
+
+    def forward(self, x, c, cls, blocks, deform_inputs1, deform_inputs2, H, W):
+        x = self._inject(x, c, deform_inputs1)
+        x = blocks(torch.cat((cls, x), 1)).last_hidden_state
+        cls, x = x[:, :1], x[:, 1:]
+        return x, self._extract(x, c, deform_inputs2, H, W), cls
