@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_deform_plan_supported / _forward / _backward, mmfs_deform_sample_forward: the image
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_dwconv_tokens_supported / _forward / _backward_workspace_bytes / _backward: the depthwise
+                                   *     convolution of the ViT-Adapter's ConvFFN in the token layout, see "ConvFFN's depthwise convolution" below
+                                   * 14 (additive): + mmfs_deform_plan_supported / _forward / _backward, mmfs_deform_sample_forward: the image
                                    *     encoder's MSDeformAttn front end, see "The image encoder's MSDeformAttn" below
                                    * 14 (additive): + mmfs_bank_quantize_fp8, mmfs_msda_forward_fp8, mmfs_sample_forward_heads_fp8:
                                    *     the inference-only fp8 (e4m3) value bank with fp32 scales, see "fp8 bank" below
@@ -593,6 +595,48 @@ int mmfs_deform_sample_forward(int dtype, const void *value, const int64_t *shap
                                const float *ref, void *out,
                                int64_t N, int64_t S, int64_t Lq, int64_t H, int64_t D, int64_t L, int64_t P,
                                int64_t Nr, int64_t Lref, int64_t R, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ConvFFN's depthwise convolution (ViT-Adapter) in the token layout (csrc/msda_dwconv.hip; additive at ABI 14).
+ * Replaces what mm_interleaved/models/encoders/vit_adapter/adapter_modules.py:64-89 runs between fc1 and fc2: three
+ * transposed copies into [B, C, h, w], three depthwise 3x3 convolutions, three transposes back, a concatenation and GELU.
+ *   x        [B, N, C]      storage type ``dtype`` (MMFS_F32 / MMFS_F16 / MMFS_BF16): L maps packed one after the other, level l =
+ *                           h_l x w_l tokens, row-major, N = sum h_l * w_l
+ *   weight   [C, 1, 3, 3]   nn.Conv2d's, read where it lies;   bias [C] or NULL
+ *   level_hw [2 * L]        HOST array (h_0, w_0, h_1, w_1, ...): the extents travel to the kernels by value -- no device table,
+ *                           no allocation, no synchronisation, so the launches can be captured into a graph
+ *   y[b, p, c] = bias[c] + sum_{ky,kx} weight[c, ky, kx] x[b, p + (ky-1, kx-1), c]: stride 1, zero padding; a tap outside its own
+ *   map is skipped (never multiplied by 0: a non-finite input reaches exactly the outputs whose window covers it).  fp32
+ *   arithmetic, ONE rounding to the storage type: y_T.
+ *   act = MMFS_DWCONV_ACT_NONE: out = y_T.   act = MMFS_DWCONV_ACT_GELU: out = gelu(y_T), the exact (erf) GELU of the ROUNDED
+ *   pre-activation, so that calls with and without ``pre`` return the same bits and the backward differentiates the number the
+ *   forward used.
+ * mmfs_dwconv_tokens_forward: out [B, N, C]; ``pre`` [B, N, C] or NULL: y_T, written only for MMFS_DWCONV_ACT_GELU (what the
+ *   backward needs).  Every element written.
+ * mmfs_dwconv_tokens_backward: from grad_out (the gradient of ``out``), x and -- MMFS_DWCONV_ACT_GELU -- pre:
+ *   g_y = grad_out * (Phi(y_T) + y_T phi(y_T)) (MMFS_DWCONV_ACT_NONE: grad_out);  grad_x[p] = sum_d w[d] g_y[p - d];
+ *   grad_weight[d] = sum_{b,p} x[p] g_y[p - d] ([C, 1, 3, 3]);  grad_bias = sum g_y ([C], or NULL), all in the storage type.
+ *   One pass over the tensors; the weight / bias gradients are a two-stage reduction through ``workspace``
+ *   (mmfs_dwconv_tokens_backward_workspace_bytes bytes, 16-byte aligned; every byte the second stage reads is written by the
+ *   first: nothing to clear) added in a fixed order -- no float atomics, bit-reproducible.
+ * mmfs_dwconv_tokens_backward_workspace_bytes: >= 0, or an MMFS_E_* of the list below.  Host only.
+ * mmfs_dwconv_tokens_supported: 1 when the kernels serve (dtype, C, L, act): C * sizeof(T) a multiple of 16, 1 <= L <= 8.  Host only.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code, MMFS_F64); MMFS_E_DIMS for a negative B, N or C, a
+ * non-positive level extent or sum h_l * w_l != N; MMFS_E_UNSUPPORTED for L outside [1, 8], C * sizeof(T) not a multiple of 16 or
+ * an unknown ``act``; MMFS_E_NULLPTR for a NULL required pointer of a non-empty problem (``level_hw`` included); MMFS_E_ALIGN for
+ * tensors not 16-byte aligned.  B * N * C == 0 returns 0 without a launch. */
+enum mmfs_dwconv_act {
+    MMFS_DWCONV_ACT_NONE = 0,
+    MMFS_DWCONV_ACT_GELU = 1
+};
+int mmfs_dwconv_tokens_supported(int dtype, int64_t C, int64_t L, int act);
+int mmfs_dwconv_tokens_forward(int dtype, const void *x, const void *weight, const void *bias, void *out, void *pre,
+                               const int64_t *level_hw, int64_t B, int64_t N, int64_t C, int64_t L, int act, void *stream);
+int64_t mmfs_dwconv_tokens_backward_workspace_bytes(int dtype, const int64_t *level_hw, int64_t B, int64_t N, int64_t C,
+                                                    int64_t L, int act);
+int mmfs_dwconv_tokens_backward(int dtype, const void *grad_out, const void *x, const void *pre, const void *weight,
+                                void *grad_x, void *grad_weight, void *grad_bias, void *workspace,
+                                const int64_t *level_hw, int64_t B, int64_t N, int64_t C, int64_t L, int act, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

@@ -2,8 +2,9 @@
 (mm_interleaved/models/encoders/vit_adapter/adapter_modules.py:15-233; 4 interaction blocks = 4 injectors +
 6 extractors per ViT forward).  Constructor signatures and ``state_dict`` keys are the reference's, so its
 checkpoints load with ``strict=True``; the ``attn`` of every block takes the fused front end
-(``MSDeformAttn.fused_front_end``, csrc/msda_deform_plan.hip).  LayerNorm, the Linear layers, GELU and the
-depthwise convolution are framework ops.
+(``MSDeformAttn.fused_front_end``, csrc/msda_deform_plan.hip) and the depthwise convolution of ``ConvFFN`` runs on the
+tokens as they lie, with its GELU (``DWConv.token_kernel``, csrc/msda_dwconv.hip).  LayerNorm, the Linear layers and
+dropout are framework ops.
 
 Differences from the reference, none of them in the numbers:
   * ``deform_inputs`` / ``get_reference_points`` build their tensors once per (image size, device) -- the level
@@ -17,6 +18,7 @@ import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp
 
+from ..functions.dwconv_func import DWConvTokensFunction, dwconv_tokens_supported
 from ..levels import make_level_tables
 from ..modules import MSDeformAttn
 
@@ -86,13 +88,34 @@ class DropPath(nn.Module):
 
 class DWConv(nn.Module):
     """Depthwise 3x3 convolution of the pyramid's tokens: the 21 n tokens are the stride-8 map (16 n = 2H x 2W), the
-    stride-16 map (4 n = H x W) and the stride-32 map (n), each convolved as an image with the same weights."""
+    stride-16 map (4 n = H x W) and the stride-32 map (n), each convolved as an image with the same weights.
+
+    ``token_kernel``: device tensors of one supported dtype, outside autocast, are convolved where they lie by
+    ``DWConvTokensFunction`` (no transposed copies, no ``cat``); everything else -- CPU tensors, autocast, widths the
+    16-byte lanes cannot take, mixed dtypes -- takes the reference's framework statement below.  The parameters stay
+    inside the ``nn.Conv2d`` either way."""
+
+    token_kernel = True
 
     def __init__(self, dim=768):
         super().__init__()
         self.dwconv = nn.Conv2d(dim, dim, 3, 1, 1, bias=True, groups=dim)
 
+    def tokens(self, x, H, W, act):
+        """The token kernel's result for ``act`` ("none" | "gelu"), or None when the route does not apply."""
+        conv = self.dwconv
+        if not (self.token_kernel and not torch.is_autocast_enabled() and x.dim() == 3
+                and dwconv_tokens_supported(x, conv.weight, conv.bias)):
+            return None
+        level_hw = ((H * 2, W * 2), (H, W), (H // 2, W // 2))
+        if sum(h * w for h, w in level_hw) != x.shape[1] or min(min(hw) for hw in level_hw) <= 0:
+            return None
+        return DWConvTokensFunction.apply(x, conv.weight, conv.bias, level_hw, act)
+
     def forward(self, x, H, W):
+        out = self.tokens(x, H, W, "none")
+        if out is not None:
+            return out
         B, N, C = x.shape
         n = N // 21
         parts = []
@@ -114,7 +137,10 @@ class ConvFFN(nn.Module):
         self.drop = nn.Dropout(drop)
 
     def forward(self, x, H, W):
-        x = self.drop(self.act(self.dwconv(self.fc1(x), H, W)))
+        x = self.fc1(x)
+        # convolution + exact GELU as one kernel call where the token kernel applies; dropout stays behind it
+        a = self.dwconv.tokens(x, H, W, "gelu") if type(self.act) is nn.GELU and self.act.approximate == "none" else None
+        x = self.drop(self.act(self.dwconv(x, H, W)) if a is None else a)
         return self.drop(self.fc2(x))
 
 

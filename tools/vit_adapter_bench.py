@@ -8,7 +8,11 @@ for the module alone and for a whole ``InteractionBlockWithCls`` (identity ``blo
 ms for forward + backward, ms for the no-grad forward (medians of interleaved rounds, with the rounds' spread
 max - min), and kernel launches per call.  Prints one JSON line.
     python tools/vit_adapter_bench.py
-    python tools/vit_adapter_bench.py prof off|on     # only runs the block (for rocprofv3 --kernel-trace --stats)
+    python tools/vit_adapter_bench.py prof off|on [framework|kernel]   # only runs the block (for rocprofv3 --kernel-trace --stats)
+    python tools/vit_adapter_bench.py dwconv          # ConvFFN's depthwise convolution: the framework
+                                                      # statement (``DWConv.token_kernel`` off, the only path before the
+                                                      # switch existed) against the token kernel, for ``ConvFFN`` alone
+                                                      # and for the block, in the same interleaved rounds
 Not the contract benchmark (bench.py)."""
 import json
 import os
@@ -19,7 +23,7 @@ from collections import namedtuple
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mm-interleaved_amd")]
 import torch  # noqa: E402
-from mmfs_amd.blocks import InteractionBlockWithCls, deform_inputs  # noqa: E402
+from mmfs_amd.blocks import ConvFFN, DWConv, InteractionBlockWithCls, deform_inputs  # noqa: E402
 from mmfs_amd.modules import MSDeformAttn  # noqa: E402
 
 dev, dt = "cuda", torch.bfloat16
@@ -73,6 +77,14 @@ def set_route(module, setting):
             m.fused_front_end, m.fused_sampler = fused, sampler
 
 
+def set_dwconv_route(module, setting):
+    """"framework" | "kernel" for every DWConv of the module; the attention modules on their defaults"""
+    set_route(module, "on_sampler")
+    for m in module.modules():
+        if isinstance(m, DWConv):
+            m.token_kernel = setting == "kernel"
+
+
 def randomise(module):
     torch.manual_seed(0)
     with torch.no_grad():
@@ -85,7 +97,7 @@ def randomise(module):
                 p.fill_(0.5)
 
 
-def candidates(module, call, inputs):
+def candidates(module, call, inputs, set_route=set_route):
     """fwd+bwd / no-grad closures per setting; the module's route is switched inside the closure (an attribute write)."""
     grads = [t for t in inputs if t.requires_grad] + list(module.parameters())
 
@@ -118,6 +130,15 @@ def measure(module, call, inputs, iters):
                               nograd_fwd={s: launches(infer(s)) for s in SETTINGS}))
 
 
+def measure_dwconv(module, call, inputs, iters):
+    train, infer = candidates(module, call, inputs, set_dwconv_route)
+    routes = ("framework", "kernel")
+    return dict(fwd_bwd=interleaved({s: train(s) for s in routes}, iters),
+                nograd_fwd=interleaved({s: infer(s) for s in routes}, iters),
+                launches=dict(fwd_bwd={s: launches(train(s)) for s in routes},
+                              nograd_fwd={s: launches(infer(s)) for s in routes}))
+
+
 def main():
     args = sys.argv[1:]
     image = torch.zeros(1, 3, IMAGE, IMAGE, device=dev)
@@ -133,10 +154,20 @@ def main():
     if args[:1] == ["prof"]:
         train, infer = candidates(block, call_block, [x, c, cls])
         f, g = train(args[1]), infer(args[1])
+        if args[2:]:                                   # the depthwise convolution's route, set once: the closures leave it alone
+            set_dwconv_route(block, args[2])
         for _ in range(30):
             f()
             g()
         torch.cuda.synchronize()
+        return
+    if args[:1] == ["dwconv"]:
+        torch.manual_seed(1)
+        ffn = ConvFFN(DIM, int(DIM * 0.25)).to(dev, dt)
+        result = dict(shape=dict(d_model=DIM, hidden=int(DIM * 0.25), B=B, tokens=n_pyr, dtype="bf16"))
+        result["conv_ffn"] = measure_dwconv(ffn, lambda m: m(c, hw, hw), [c], 20)
+        result["interaction_block_cls"] = measure_dwconv(block, call_block, [x, c, cls], 10)
+        print(json.dumps(result))
         return
     inj = MSDeformAttn(d_model=DIM, n_levels=3, n_heads=HEADS, n_points=P, ratio=0.5).to(dev, dt)
     ext = MSDeformAttn(d_model=DIM, n_levels=1, n_heads=HEADS, n_points=P, ratio=0.5).to(dev, dt)
