@@ -261,7 +261,8 @@ plan_backward_kernel(const T *__restrict__ grad_loc, const T *__restrict__ grad_
         slab[grp][gl][P + 2 * p] = t_off[2 * p];
         slab[grp][gl][P + 2 * p + 1] = t_off[2 * p + 1];
     }
-    seg_key[grp][gl] = (act && t_rp >= 0) ? (((long long)nb * d.H + h) << 20 | (long long)t_rp) : -1LL - grp;
+    // (nb * H + h < 2^31 and t_rp < M <= 2^31 - 1 by check_dims: 32 bits each, no two rows share a key)
+    seg_key[grp][gl] = (act && t_rp >= 0) ? (((long long)nb * d.H + h) << 32 | (long long)t_rp) : -1LL - grp;
     __syncthreads();
     if (act && t_rp >= 0 && (grp == 0 || seg_key[grp - 1][gl] != seg_key[grp][gl])) {
         const long long key = seg_key[grp][gl];
