@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_dwconv_tokens_supported / _forward / _backward_workspace_bytes / _backward: the depthwise
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_pyramid_head_supported / _forward / _backward: the ViT-Adapter's output pyramid from the
+                                   *     tokens, packed for the feature bank, see "The adapter's output pyramid" below
+                                   * 14 (additive): + mmfs_dwconv_tokens_supported / _forward / _backward_workspace_bytes / _backward: the depthwise
                                    *     convolution of the ViT-Adapter's ConvFFN in the token layout, see "ConvFFN's depthwise convolution" below
                                    * 14 (additive): + mmfs_deform_plan_supported / _forward / _backward, mmfs_deform_sample_forward: the image
                                    *     encoder's MSDeformAttn front end, see "The image encoder's MSDeformAttn" below
@@ -637,6 +639,48 @@ int64_t mmfs_dwconv_tokens_backward_workspace_bytes(int dtype, const int64_t *le
 int mmfs_dwconv_tokens_backward(int dtype, const void *grad_out, const void *x, const void *pre, const void *weight,
                                 void *grad_x, void *grad_weight, void *grad_bias, void *workspace,
                                 const int64_t *level_hw, int64_t B, int64_t N, int64_t C, int64_t L, int act, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The adapter's output pyramid (ViT-Adapter) from the tokens, packed token-major (csrc/mmfs_pyramid.hip; additive at ABI 14).
+ * Replaces the tail of mm_interleaved/models/encoders/vit_adapter/vit_adapter_hf.py:137-153 (transposed copies of the adapter's
+ * tokens and the four ViT maps, adapter_up, three bilinear resizes, five adds), the position add of encoders/visual_tokenizer.py:
+ * 74-82 and the transposition back into the bank's layout.  H x W is the ViT map, both even.
+ *   c     [B, 21 H W / 4, C]  the adapter's tokens c2 (2H x 2W) | c3 (H x W) | c4 (H/2 x W/2), storage type ``dtype``
+ *   x1..x4 [B, H W, C]        the ViT's tokens after each interaction block
+ *   up    [B, 4 H W, 4 C]     adapter_up as a GEMM on the c2 tokens, bias included: columns (di, dj, o); output pixel
+ *                             (2i + di, 2j + dj) of level 1 reads row (i, j), column block (di, dj)
+ *   c1    [B, C, 4H, 4W]      the spatial prior's first map: MMFS_PYRAMID_C1_NCHW contiguous, MMFS_PYRAMID_C1_NHWC channels_last
+ *                             memory (i.e. [B, 4H, 4W, C])
+ *   pos1..pos4 [h_l w_l, C]   fp32 tables, each or NULL
+ *   levels                    bit l - 1 selects level l; the packed row holds the selected levels only, in order
+ *   out   [B, S, C]           S = sum of the selected h_l w_l, (h_l, w_l) = (4H, 4W), (2H, 2W), (H, W), (H/2, W/2):
+ *     level 1 = up + c1 + bilinear x4 (x1) + pos1;  level 2 = c2 + bilinear x2 (x2) + pos2;  level 3 = c3 + x3 + pos3;
+ *     level 4 = c4 + mean 2x2 (x4) + pos4.   The resizes are F.interpolate's (bilinear, align_corners = False).  fp32 arithmetic,
+ *     ONE rounding to the storage type.  A tap of weight 0 (the second tap of the clamped first rows / columns) is not read: a
+ *     non-finite input reaches exactly the outputs that hold it under a non-zero weight.  Every element written.
+ * mmfs_pyramid_head_backward: from grad_out [B, S, C]: grad_up [B, 4HW, 4C] and grad_c1 (c1's layout) are level 1's rows
+ *   permuted; grad_x1 / grad_x2 are gathered by their owner from at most 8 x 8 / 4 x 4 gradient pixels; grad_x3 is level 3's
+ *   rows; grad_x4[i, j] = 0.25 grad_4[i / 2, j / 2].  No atomics, nothing to clear, bit-reproducible.  The gradient of ``c`` is
+ *   levels 2..4 of grad_out itself and is left to the caller.  An output pointer that is NULL is a gradient nobody needs: it
+ *   is not computed.  Pointers of levels that are not selected are not looked at, by either call (alignment included).
+ * mmfs_pyramid_head_supported: 1 when the kernels serve (dtype, C, H, W, levels): f32 / f16 / bf16, C * sizeof(T) a multiple
+ *   of 16, H and W even and >= 2, 1 <= levels <= 15.  Host only.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code, MMFS_F64); MMFS_E_DIMS for a negative B, H, W or C or
+ * extents beyond the index range (H, W > 4096); MMFS_E_UNSUPPORTED for what the query refuses or an unknown ``c1_layout``;
+ * MMFS_E_NULLPTR for a NULL input (or ``out`` / ``grad_out``) of a selected level; MMFS_E_ALIGN for tensors of selected levels
+ * that are not 16-byte aligned.  B * C == 0 returns 0 without a launch. */
+enum mmfs_pyramid_c1_layout {
+    MMFS_PYRAMID_C1_NCHW = 0,
+    MMFS_PYRAMID_C1_NHWC = 1
+};
+int mmfs_pyramid_head_supported(int dtype, int64_t C, int64_t H, int64_t W, int levels);
+int mmfs_pyramid_head_forward(int dtype, const void *c, const void *x1, const void *x2, const void *x3, const void *x4,
+                              const void *up, const void *c1, const float *pos1, const float *pos2, const float *pos3,
+                              const float *pos4, void *out, int64_t B, int64_t H, int64_t W, int64_t C, int levels,
+                              int c1_layout, void *stream);
+int mmfs_pyramid_head_backward(int dtype, const void *grad_out, void *grad_up, void *grad_c1, void *grad_x1, void *grad_x2,
+                               void *grad_x3, void *grad_x4, int64_t B, int64_t H, int64_t W, int64_t C, int levels,
+                               int c1_layout, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

@@ -1,5 +1,5 @@
 """The callers either side of the op."""
 from .llama_mmfs import LlamaMMFSAttention, LlamaMMFSSchedule, MMFSRMSNorm, ProjectedBank  # noqa: F401
 from .sd_mmfs import MMFSBlock, MMFSNet  # noqa: F401
-from .vit_adapter import (ConvFFN, DWConv, Extractor, Injector, InteractionBlock, InteractionBlockWithCls,  # noqa: F401
-                          deform_inputs, get_reference_points)
+from .vit_adapter import (AdapterPyramidHead, ConvFFN, DWConv, Extractor, Injector, InteractionBlock,  # noqa: F401
+                          InteractionBlockWithCls, deform_inputs, get_reference_points, pyramid_pos_tables)

@@ -11,15 +11,21 @@ Differences from the reference, none of them in the numbers:
     tables through ``levels.make_level_tables``, which also marks them as canonically packed for the op's backward --
     instead of six tensors per call;
   * stochastic depth is a module of this file (no ``timm`` import).
+
+``AdapterPyramidHead`` is the stretch behind the blocks: from the adapter's tokens and the four ViT maps to the output
+pyramid with its position tables, packed token-major as the feature bank reads it (csrc/mmfs_pyramid.hip).
 """
+import math
 from functools import partial
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
 from ..functions.dwconv_func import DWConvTokensFunction, dwconv_tokens_supported
-from ..levels import make_level_tables
+from ..functions.pyramid_func import PyramidHeadFunction, level_mask, level_sizes, pyramid_head_supported
+from ..levels import cache_epoch, make_level_tables, tensor_version
 from ..modules import MSDeformAttn
 
 _ref_cache = {}
@@ -245,3 +251,134 @@ class InteractionBlockWithCls(InteractionBlock):
         x = blocks(torch.cat((cls, x), 1)).last_hidden_state
         cls, x = x[:, :1], x[:, 1:]
         return x, self._extract(x, c, deform_inputs2, H, W), cls
+
+
+# ------------------------------------------------------------------ the output pyramid
+_pos_cache = {}
+
+
+def pyramid_pos_tables(pos_embed, H, W):
+    """The position tables of the four output levels, fp32 [h_l * w_l, C] each: the reference's
+    ``get_abs_pos(pos_embed[1:], h * w)`` (models/utils/pos_embed.py:16-40 as encoders/visual_tokenizer.py:74-82 calls
+    it) -- the square table resized bicubically in fp32 to the level's side.  ``pos_embed`` is the [g * g, C] table, or
+    the reference's parameter with its class-token row in front ([1 + g * g, C]; the row is dropped).  Built once per
+    (table, H, W) on the table's device and kept until ``mmfs_amd.invalidate_caches()``.  The reference's resize knows square maps only: H == W."""
+    if H != W:
+        raise ValueError(f"position tables are defined for square maps only (H = {H}, W = {W})")
+    # keyed like the package's other kept tensors (levels.py): pointer, version counter and the epoch that
+    # ``mmfs_amd.invalidate_caches()`` moves; an entry keeps its table alive, so the address cannot be handed to another
+    key = (pos_embed.data_ptr(), tensor_version(pos_embed), tuple(pos_embed.shape), pos_embed.dtype, str(pos_embed.device), H)
+    hit = _pos_cache.get(key)
+    if hit is not None and hit[0] is pos_embed and hit[1] == cache_epoch():
+        return hit[2]
+    # (kept tensors: built outside inference mode, see levels.make_level_tables)
+    with torch.inference_mode(False), torch.no_grad():
+        table = pos_embed.detach().float()
+        n = table.shape[0]
+        if math.isqrt(n) ** 2 != n and math.isqrt(n - 1) ** 2 == n - 1:
+            table = table[1:]
+        src = math.isqrt(table.shape[0])
+        tabs = []
+        for h, _ in level_sizes(H, W):
+            if h == src:
+                tabs.append(table.contiguous())
+                continue
+            t = F.interpolate(table.reshape(1, src, src, -1).permute(0, 3, 1, 2), size=(h, h), mode="bicubic",
+                              align_corners=False)
+            tabs.append(t.permute(0, 2, 3, 1).flatten(0, 2).contiguous())
+        tabs = tuple(tabs)
+    if len(_pos_cache) >= 16:
+        _pos_cache.clear()
+    _pos_cache[key] = (pos_embed, cache_epoch(), tabs)
+    return tabs
+
+
+class AdapterPyramidHead(nn.Module):
+    """From the adapter's tokens to the output pyramid (vit_adapter_hf.py:137-153 and the position add of
+    visual_tokenizer.py:74-82):
+        c1 = adapter_up(c2) + c1 + bilinear x4 (x1),  c2 + bilinear x2 (x2),  c3 + x3,  c4 + bilinear x0.5 (x4),
+    each plus its position table.  ``adapter_up`` is the reference's ``nn.ConvTranspose2d(dim, dim, 2, 2)`` with the
+    reference's state-dict keys.
+
+    forward(c, outs, c1, H, W, pos_embed=None, levels=(0, 1, 2, 3), packed=True):
+      c      [B, 21 HW / 4, C]  the adapter's tokens c2 | c3 | c4 behind the last interaction block
+      outs   four [B, HW, C]    the ViT's tokens behind each interaction block (the reference's ``outs`` before their
+                                transposes); entries of levels that are not produced may be None
+      c1     [B, C, 4H, 4W]     the spatial prior's first map, contiguous or channels_last (None without level 0)
+      pos_embed                 None, the square sin-cos table (see ``pyramid_pos_tables``) or four ready tables
+      levels                    which of (c1, c2, c3, c4) to produce, e.g. those whose side the decoder reads
+    -> ``packed``: [B, sum h_l w_l, C], the levels one after the other, token-major -- what ``bank.llm_feature_bank`` and
+    ``bank.pack_image_levels`` speak;  else the reference's list of [B, C, h_l, w_l] (on the kernel route views of the
+    packed tensor).
+
+    ``token_kernel``: device tensors of one supported dtype, outside autocast, take ``PyramidHeadFunction`` -- the
+    transposed convolution becomes one GEMM on the c2 tokens (bias included; its parameter gradients are the GEMM's)
+    and everything else one pass that reads each input once and writes the packed pyramid once.  CPU tensors, autocast,
+    fp64, mixed dtypes and widths the 16-byte lanes cannot take run the reference's framework statement.  On by
+    default (keep rule and measurements: DESIGN.md 4.13, profiles/vit_adapter.md)."""
+
+    token_kernel = True
+
+    def __init__(self, dim):
+        super().__init__()
+        self.adapter_up = nn.ConvTranspose2d(dim, dim, 2, 2)
+
+    def up_tokens(self, c2):
+        """adapter_up on the tokens of the 2H x 2W map: [B, n, C] -> [B, n, 4C] with columns (di, dj, o) -- output pixel
+        (2i + di, 2j + dj), channel o, of token (i, j)."""
+        w, b = self.adapter_up.weight, self.adapter_up.bias
+        C = w.shape[0]
+        w2 = w.permute(0, 2, 3, 1).reshape(C, 4 * w.shape[1])
+        return torch.addmm(b.repeat(4), c2.reshape(-1, C), w2).view(c2.shape[0], c2.shape[1], w2.shape[1])
+
+    def forward(self, c, outs, c1, H, W, pos_embed=None, levels=(0, 1, 2, 3), packed=True):
+        levels = tuple(sorted(set(int(l) for l in levels)))
+        mask = level_mask(levels)
+        if mask == 0:
+            raise ValueError("levels: at least one of 0..3")
+        sizes = level_sizes(H, W)
+        if pos_embed is None or isinstance(pos_embed, (tuple, list)):
+            pos = None if pos_embed is None else tuple(pos_embed)
+        else:
+            pos = pyramid_pos_tables(pos_embed, H, W)
+        outs = tuple(outs)
+        if c.dim() != 3:
+            raise ValueError(f"c: [B, 21 HW / 4, C] expected, got {tuple(c.shape)}")
+        if pos is not None and any(t.device != c.device for l, t in enumerate(pos) if l in levels):
+            raise ValueError(f"position tables on {pos[levels[0]].device}, tokens on {c.device}: move pos_embed to the tokens' device")
+        B, _, C = c.shape
+        if (self.token_kernel and not torch.is_autocast_enabled()
+                and self.adapter_up.weight.dtype == c.dtype and self.adapter_up.weight.device == c.device
+                and pyramid_head_supported(c, outs, c1, pos, H, W, mask)):
+            up = self.up_tokens(c[:, :4 * H * W]) if mask & 1 else None
+            out = PyramidHeadFunction.apply(c, *outs, up, c1, pos, H, W, mask)
+            if packed:
+                return out
+            feats, lo = [], 0
+            for l in levels:
+                h, w = sizes[l]
+                feats.append(out[:, lo:lo + h * w].transpose(1, 2).unflatten(2, (h, w)))
+                lo += h * w
+            return feats
+        # the reference's statement
+        n2, n3 = 4 * H * W, H * W
+        img = lambda t, hw: t.transpose(1, 2).reshape(B, C, *hw).contiguous()     # noqa: E731
+        feats = []
+        for l in levels:
+            if l == 0:
+                f = self.adapter_up(img(c[:, :n2], sizes[1])) + c1
+                f = f + F.interpolate(img(outs[0], sizes[2]), scale_factor=4, mode="bilinear", align_corners=False)
+            elif l == 1:
+                f = img(c[:, :n2], sizes[1]) + F.interpolate(img(outs[1], sizes[2]), scale_factor=2, mode="bilinear",
+                                                             align_corners=False)
+            elif l == 2:
+                f = img(c[:, n2:n2 + n3], sizes[2]) + img(outs[2], sizes[2])
+            else:
+                f = img(c[:, n2 + n3:], sizes[3]) + F.interpolate(img(outs[3], sizes[2]), scale_factor=0.5,
+                                                                  mode="bilinear", align_corners=False)
+            if pos is not None:
+                f = f + pos[l].to(f.dtype).reshape(*sizes[l], C).permute(2, 0, 1)
+            feats.append(f)
+        if packed:
+            return torch.cat([f.flatten(2).transpose(1, 2) for f in feats], 1)
+        return feats

@@ -13,6 +13,12 @@ max - min), and kernel launches per call.  Prints one JSON line.
                                                       # statement (``DWConv.token_kernel`` off, the only path before the
                                                       # switch existed) against the token kernel, for ``ConvFFN`` alone
                                                       # and for the block, in the same interleaved rounds
+    python tools/vit_adapter_bench.py pyramid [nhwc]  # the output pyramid: the framework statement
+                                                      # (``AdapterPyramidHead.token_kernel`` off) against the token
+                                                      # kernels, all four levels and without the 64^2 level, c1 in NCHW
+                                                      # (or channels_last), in the same interleaved rounds; + the
+                                                      # kernels' algorithmic bytes
+    python tools/vit_adapter_bench.py prof pyramid framework|kernel [all|no1] [nhwc]   # only runs the head
 Not the contract benchmark (bench.py)."""
 import json
 import os
@@ -23,7 +29,7 @@ from collections import namedtuple
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mm-interleaved_amd")]
 import torch  # noqa: E402
-from mmfs_amd.blocks import ConvFFN, DWConv, InteractionBlockWithCls, deform_inputs  # noqa: E402
+from mmfs_amd.blocks import AdapterPyramidHead, ConvFFN, DWConv, InteractionBlockWithCls, deform_inputs  # noqa: E402
 from mmfs_amd.modules import MSDeformAttn  # noqa: E402
 
 dev, dt = "cuda", torch.bfloat16
@@ -139,8 +145,81 @@ def measure_dwconv(module, call, inputs, iters):
                               nograd_fwd={s: launches(infer(s)) for s in routes}))
 
 
+def pyramid_bytes(Bn, H, W, C, mask, nhwc, tables=True, e=2):
+    """Algorithmic bytes of the pyramid head's kernels from the shapes: every input read once, every output written
+    once, position tables (fp32) once per call; the backward's level-1 rows are read by each kernel that needs them.
+    The forward's framework ops in front of level 1 (the copy of c2 and the GEMM) are listed too."""
+    px = [16 * H * W, 4 * H * W, H * W, H * W // 4]
+    on = [(mask >> l) & 1 for l in range(4)]
+    row = C * e * Bn
+    tab = [C * 4 * n if tables else 0 for n in px]
+    lvl1 = (3 * px[0] + px[2]) * row + tab[0]                                  # up, c1, out + x1
+    rows = sum((2 * px[l] + px[2]) * row + tab[l] for l in (1, 2, 3) if on[l])   # c_l, out + x_l
+    out = {"pyramid_fwd_rows": rows + (lvl1 if on[0] and nhwc else 0)}
+    if on[0] and not nhwc:
+        out["pyramid_fwd_c1_nchw"] = lvl1
+    back = sum((px[l] + px[2]) * row for l in (1, 2, 3) if on[l])              # g_l read, g_x_l written
+    if on[0]:
+        back += (2 * px[0] + px[0] + px[2]) * row + (px[0] * row if nhwc else 0)   # g_1 -> g_up (+ g_c1); g_1 -> g_x1
+        if not nhwc:
+            out["pyramid_bwd_c1_nchw"] = 2 * px[0] * row
+    out["pyramid_bwd_rows"] = back
+    if on[0]:       # the framework ops in front of level 1: c2 gathered out of c (a copy for B > 1), then the GEMM
+        out["adapter_up_c2_copy"] = 2 * px[1] * row
+        out["adapter_up_gemm"] = (px[1] + px[0]) * row + 4 * C * C * e
+    return out
+
+
+def pyramid_setup(nhwc):
+    torch.manual_seed(2)
+    H = W = IMAGE // 16
+    head = AdapterPyramidHead(DIM).to(dev, dt)
+    rn = lambda *s: torch.randn(*s, device=dev, dtype=dt).requires_grad_(True)     # noqa: E731
+    c = rn(B, 21 * H * W // 4, DIM)
+    xs = [rn(B, H * W, DIM) for _ in range(4)]
+    c1 = torch.randn(B, DIM, 4 * H, 4 * W, device=dev, dtype=dt)
+    if nhwc:
+        c1 = c1.contiguous(memory_format=torch.channels_last)
+    c1.requires_grad_(True)
+    pos = torch.randn(1 + 16 * 16, DIM, device=dev)              # the reference's table: a 16 x 16 grid behind a class-token row
+    return head, c, xs, c1, pos, H, W
+
+
+def set_pyramid_route(module, setting):
+    module.token_kernel = setting == "kernel"
+
+
+def main_pyramid(args):
+    nhwc = "nhwc" in args
+    head, c, xs, c1, pos, H, W = pyramid_setup(nhwc)
+    masks = {"all": (0, 1, 2, 3), "no1": (1, 2, 3)}
+    if args[:1] == ["prof"]:
+        levels = masks["no1" if "no1" in args else "all"]
+        train, infer = candidates(head, lambda m: m(c, xs, c1, H, W, pos_embed=pos, levels=levels), [c, c1] + xs,
+                                  set_pyramid_route)
+        f, g = train(args[2]), infer(args[2])
+        for _ in range(30):
+            f()
+            g()
+        torch.cuda.synchronize()
+        return
+    routes = ("framework", "kernel")
+    result = dict(shape=dict(C=DIM, H=H, W=W, B=B, dtype="bf16", c1="channels_last" if nhwc else "nchw", tables=True))
+    for name, levels in masks.items():
+        train, infer = candidates(head, lambda m: m(c, xs, c1, H, W, pos_embed=pos, levels=levels), [c, c1] + xs,
+                                  set_pyramid_route)
+        result[name] = dict(fwd_bwd=interleaved({s: train(s) for s in routes}, 10),
+                            nograd_fwd=interleaved({s: infer(s) for s in routes}, 10),
+                            launches=dict(fwd_bwd={s: launches(train(s)) for s in routes},
+                                          nograd_fwd={s: launches(infer(s)) for s in routes}),
+                            kernel_bytes=pyramid_bytes(B, H, W, DIM, sum(1 << l for l in levels), nhwc))
+    print(json.dumps(result))
+
+
 def main():
     args = sys.argv[1:]
+    if args[:1] == ["pyramid"] or args[:2] == ["prof", "pyramid"]:
+        return main_pyramid(args[1:] if args[0] == "pyramid" else args)
     image = torch.zeros(1, 3, IMAGE, IMAGE, device=dev)
     d1, d2 = deform_inputs(image)
     hw = IMAGE // 16
