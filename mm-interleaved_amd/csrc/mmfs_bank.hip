@@ -39,10 +39,6 @@ struct BankLevels {
     BankLevel lv[kMaxBankLevels];
 };
 
-template <int BYTES> struct Word;
-template <> struct Word<2> { typedef uint16_t type; };
-template <> struct Word<4> { typedef uint32_t type; };
-
 __device__ __forceinline__ int level_of(const BankLevels &L, int tile)
 {
     int l = 0;

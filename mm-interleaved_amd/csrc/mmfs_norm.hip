@@ -33,13 +33,6 @@ template <typename T> struct NormIO {
     static __device__ __forceinline__ float round(float v) { return (float)(T)v; }
 };
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <typename T, int NV>
 __global__ void __launch_bounds__(kNormThreads)
 rmsnorm_fwd(const T *__restrict__ x, const T *__restrict__ w, T *__restrict__ y, float *__restrict__ rstd_out,

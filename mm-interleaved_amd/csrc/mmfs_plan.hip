@@ -20,9 +20,9 @@
 // the 2^k >= n*L lanes of an item reduce with wave shuffles.  The backward walks runs of consecutive
 // queries and keeps the gradient of the lane's table row in registers (the relative position of
 // an image changes at most once per image along the sequence), flushing it with a few float atomics.
-#include "../../include/mmfs_msda.h"
 #include "msda_env.h"
-#include "msda_device.h"
+#include "msda_gather.h"
+#include "msda_host.h"
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -41,38 +41,102 @@ struct PlanDims {
     int ld_toff, ld_tatt;   // the same for the two tables' rows (plan kernels; the sampler's tables are packed)
 };
 
-// lane group: G = 2^k lanes, one per (image, level) row of P points; reductions stay inside it
-template <int G> __device__ __forceinline__ float group_max(float v)
+// ---------------------------------------------------------------- the plan row
+// One (image, level) row of an item's plan, evaluated by plan_forward_kernel, mmfs_sample_fwd and mmfs_sample_decode
+// through THESE functions: the fused samplers' locations and weights are the plan kernel's bits by construction.
+
+// lane group: G = 2^k lanes, one per (image, level) row of P points; reductions stay inside it.  G known at compile
+// time (the plan kernels) or not (the samplers): the same butterfly, the same order of sums (msda_device.h)
+template <int G> struct LaneGroup {
+    __device__ __forceinline__ float max(float v) const { return group_max<G>(v); }
+    __device__ __forceinline__ float add(float v) const { return group_add<G>(v); }
+};
+struct LaneGroupRt {
+    int G;
+    __device__ __forceinline__ float max(float v) const { return group_max(v, G); }
+    __device__ __forceinline__ float add(float v) const { return group_add(v, G); }
+};
+
+// logits of row gl (= image k, level l) of the item (nb, q, h): att_q + table row + visibility penalty.  Returns the
+// image's relative position (its table row; 0 = not visible, mmfs.py:203-218)
+//   att_q [N, Lq, H, L, P]  att_tab [M, H, L, P]   (the dead sink column is not computed at all)
+template <typename T, int P>
+__device__ __forceinline__ int64_t row_logits(const T *__restrict__ att_q, const T *__restrict__ att_tab,
+                                              const int64_t *__restrict__ relpos, const PlanDims &d, int nb, int q, int h,
+                                              int gl, float (&lg)[P])
 {
+    const int k = gl / d.L, l = gl % d.L;
+    const int64_t r = relpos[((int64_t)nb * d.Lr + (d.Lr == 1 ? 0 : q)) * d.n + k];
+    float a[P], t[P];
+    load_row<T, P>(att_q + ((int64_t)nb * d.Lq + q) * d.ld_att + (h * d.L + l) * P, a);
+    load_row<T, P>(att_tab + r * d.ld_tatt + (h * d.L + l) * P, t);
+    const float pen = r == 0 ? -10000.f : 0.f;
 #pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <int G> __device__ __forceinline__ float group_add(float v)
-{
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+    for (int p = 0; p < P; ++p) lg[p] = a[p] + t[p] + pen;
+    return r;
 }
 
-// P elements of T <-> floats, as one aligned vector access (P * sizeof(T) is 8, 16 or 32 bytes)
-template <typename T, int P> __device__ __forceinline__ void load_row(const T *p, float (&o)[P])
+// Softmax statistics of an item over its rows' logits and one sink slot per row (mmfs.py:225): every lane of the group
+// brings its row's logits (act false: a lane without a row).  Leaves exp(logit - m) in lg (0 without a row).
+template <int P, typename Grp>
+__device__ __forceinline__ void sink_softmax(float (&lg)[P], bool act, float sink_logit, const Grp grp,
+                                             float &m, float &inv, float &sink_sum)
 {
-    T tmp[P];
-    __builtin_memcpy(tmp, __builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), P * sizeof(T));
+    m = sink_logit;
 #pragma unroll
-    for (int i = 0; i < P; ++i) o[i] = to_f32(tmp[i]);
+    for (int p = 0; p < P; ++p) {
+        if (!act) lg[p] = -INFINITY;
+        m = fmaxf(m, lg[p]);
+    }
+    m = grp.max(m);
+    float z = act ? __expf(sink_logit - m) : 0.f;           // this row's sink slot
+    const float my_sink = z;
+#pragma unroll
+    for (int p = 0; p < P; ++p) { lg[p] = __expf(lg[p] - m); z += lg[p]; }
+    z = grp.add(z);
+    inv = 1.f / z;
+    sink_sum = grp.add(my_sink) * inv;
 }
-template <typename T, int P> __device__ __forceinline__ void store_row(T *p, const float (&v)[P])
+
+// the row's offsets (query side + the table row of relative position r), reference point and offset scale:
+// loc = ref + (offset_q + offset_table) * ratio_l / (W, H)        (mmfs.py:193-198, 243-250)
+template <typename T, int P>
+__device__ __forceinline__ void row_geometry(const T *__restrict__ off_q, const T *__restrict__ off_tab,
+                                             const float *__restrict__ ref, const float *__restrict__ ratios,
+                                             const PlanDims &d, int nb, int q, int h, int gl, int64_t r, float Hl, float Wl,
+                                             float (&oq)[2 * P], float (&ot)[2 * P], float &rx, float &ry, float &sx, float &sy)
 {
-    T tmp[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) tmp[i] = (T)v[i];
-    __builtin_memcpy(__builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), tmp, P * sizeof(T));
+    load_row<T, 2 * P>(off_q + ((int64_t)nb * d.Lq + q) * d.ld_off + h * 2 * P, oq);
+    load_row<T, 2 * P>(off_tab + r * d.ld_toff + h * 2 * P, ot);
+    rx = ref[((int64_t)(d.Nr == 1 ? 0 : nb) * d.Lq + q) * 2];
+    ry = ref[((int64_t)(d.Nr == 1 ? 0 : nb) * d.Lq + q) * 2 + 1];
+    const int l = gl % d.L;
+    sx = ratios[l] / Wl; sy = ratios[l] / Hl;
+}
+
+// A point's weight and location as the numbers of the storage type (held in floats); e: sink_softmax's exp(logit - m).
+// An fp32 result, THEN rounded to the storage type.  For fp16 storage the compiler folds ``(half)fma(a, b, c)`` into
+// v_fma_mixlo_f16, which rounds the exact sum ONCE; with offsets that are halves and scales that are powers of two the
+// fp32 result often sits exactly on a half-precision tie, where the two roundings part (a golden: one location in 4608
+// -> two outputs one unit apart between a kernel that rounds twice and one that rounds once).
+// The opaque register keeps the fp32 rounding.
+template <typename T> __device__ __forceinline__ float point_weight(float e, float inv)
+{
+    float wgt = e * inv;
+    asm volatile("" : "+v"(wgt));
+    return to_f32((T)wgt);
+}
+// (o: the row's offsets as (x, y) pairs, query side and table side; p: the point)
+template <typename T, int P>
+__device__ __forceinline__ void point_location(const float (&oq)[2 * P], const float (&ot)[2 * P], int p, float rx, float ry,
+                                               float sx, float sy, float &x, float &y)
+{
+    float lx = fmaf(oq[2 * p] + ot[2 * p], sx, rx), ly = fmaf(oq[2 * p + 1] + ot[2 * p + 1], sy, ry);
+    asm volatile("" : "+v"(lx), "+v"(ly));
+    x = to_f32((T)lx); y = to_f32((T)ly);
 }
 
 // Forward: lane <-> one (item, image, level) row of P logits; G lanes (>= n*L) form an item.
-//   att_q [N, Lq, H, L, P]  att_tab [M, H, L, P]   (the dead sink column is not computed at all)
 template <typename T, int P, int G>
 __global__ void __launch_bounds__(kThreads)
 plan_forward_kernel(const T *__restrict__ off_q, const T *__restrict__ att_q,
@@ -92,55 +156,23 @@ plan_forward_kernel(const T *__restrict__ off_q, const T *__restrict__ att_q,
     const int64_t nq = it / d.H;
     const int q = (int)(nq % d.Lq);
     const int nb = (int)(nq / d.Lq);
-    const int k = act ? gl / d.L : 0, l = act ? gl % d.L : 0;
-    const int64_t r = relpos[((int64_t)nb * d.Lr + (d.Lr == 1 ? 0 : q)) * d.n + k];
-    const float sink_logit = -logf((float)nL);
 
-    float lg[P];
-    float m = sink_logit;
-    if (act) {
-        float a[P], t[P];
-        load_row<T, P>(att_q + nq * d.ld_att + (h * d.L + l) * P, a);
-        load_row<T, P>(att_tab + r * d.ld_tatt + (h * d.L + l) * P, t);
-        const float pen = r == 0 ? -10000.f : 0.f;          // image not visible (mmfs.py:203-218)
-#pragma unroll
-        for (int p = 0; p < P; ++p) { lg[p] = a[p] + t[p] + pen; m = fmaxf(m, lg[p]); }
-    } else {
-#pragma unroll
-        for (int p = 0; p < P; ++p) lg[p] = -INFINITY;
-    }
-    m = group_max<G>(m);
-    float z = act ? __expf(sink_logit - m) : 0.f;           // this row's sink slot (mmfs.py:225)
-    const float my_sink = z;
-#pragma unroll
-    for (int p = 0; p < P; ++p) { lg[p] = __expf(lg[p] - m); z += lg[p]; }
-    z = group_add<G>(z);
-    const float inv = 1.f / z;
-    const float sink_sum = group_add<G>(my_sink) * inv;
+    float lg[P], m, inv, sink_sum;
+    int64_t r = 0;
+    if (act) r = row_logits<T, P>(att_q, att_tab, relpos, d, nb, q, h, gl, lg);
+    sink_softmax<P>(lg, act, -logf((float)nL), LaneGroup<G>(), m, inv, sink_sum);
     if (item_ok && gl == 0) sink[item] = sink_sum;
     if (!act) return;
+    float w[P];
 #pragma unroll
-    for (int p = 0; p < P; ++p) { lg[p] *= inv; asm volatile("" : "+v"(lg[p])); }       // (fp32 product, then rounded: see below)
+    for (int p = 0; p < P; ++p) w[p] = point_weight<T>(lg[p], inv);
     const int64_t row = item * nL + gl;
-    store_row<T, P>(attn + row * P, lg);
-    // locations: ref + (offset_q + offset_table) * ratio_l / (W, H)        (mmfs.py:193-198, 243-250)
-    float oq[2 * P], ot[2 * P], xy[2 * P];
-    load_row<T, 2 * P>(off_q + nq * d.ld_off + h * 2 * P, oq);
-    load_row<T, 2 * P>(off_tab + r * d.ld_toff + h * 2 * P, ot);
-    const float rx = ref[((int64_t)(d.Nr == 1 ? 0 : nb) * d.Lq + q) * 2];
-    const float ry = ref[((int64_t)(d.Nr == 1 ? 0 : nb) * d.Lq + q) * 2 + 1];
-    const float sx = ratios[l] / (float)shapes[2 * gl + 1], sy = ratios[l] / (float)shapes[2 * gl];
+    store_row<T, P>(attn + row * P, w);
+    float oq[2 * P], ot[2 * P], xy[2 * P], rx, ry, sx, sy;
+    row_geometry<T, P>(off_q, off_tab, ref, ratios, d, nb, q, h, gl, r, (float)shapes[2 * gl], (float)shapes[2 * gl + 1],
+                       oq, ot, rx, ry, sx, sy);
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        // An fp32 result, THEN rounded to the storage type -- in both kernels that evaluate the plan (here and
-        // mmfs_sample_fwd).  For fp16 storage the compiler folds ``(half)fma(a, b, c)`` into v_fma_mixlo_f16, which rounds
-        // the exact sum ONCE; with offsets that are halves and scales that are powers of two the fp32 result often sits
-        // exactly on a half-precision tie, where the two roundings part (a golden: one location in 4608 -> two outputs one
-        // unit apart between the fused sampler and plan + op).  The opaque register keeps the fp32 rounding.
-        xy[2 * p] = fmaf(oq[2 * p] + ot[2 * p], sx, rx);
-        xy[2 * p + 1] = fmaf(oq[2 * p + 1] + ot[2 * p + 1], sy, ry);
-        asm volatile("" : "+v"(xy[2 * p]), "+v"(xy[2 * p + 1]));
-    }
+    for (int p = 0; p < P; ++p) point_location<T, P>(oq, ot, p, rx, ry, sx, sy, xy[2 * p], xy[2 * p + 1]);
     store_row<T, 2 * P>(loc + row * 2 * P, xy);
 }
 
@@ -283,23 +315,13 @@ plan_backward_kernel(const T *__restrict__ grad_loc, const T *__restrict__ grad_
 // SURVEY.md 8f N1, second half: the sampling plan feeds the sampler directly -- the locations and weights
 // [N, Lq, H, n*L, P(, 2)] never exist in HBM.  This is msda_fwd_vec (csrc/msda_fwd.hip) with its staging
 // replaced: instead of reading loc / attn it evaluates the plan for its 256 / LPI queries of one (sample,
-// head) from the heads' outputs and table rows, in the SAME arithmetic as plan_forward_kernel (same lane
-// groups, same reduction order, results rounded to the storage type before use), so the output is bit-
-// identical to plan_forward + ms_deform_attn_forward.  Forward only: the backward needs loc / attn as
+// head) from the heads' outputs and table rows with the plan row's functions above (plan_forward_kernel's lane
+// groups and reduction order, results rounded to the storage type before use) and walks the records with
+// msda_fwd_vec's functions (msda_gather.h), so the output is bit-identical to plan_forward +
+// ms_deform_attn_forward.  Forward only: the backward needs loc / attn as
 // tensors (the sort scans them, the plan backward reads the weights), so training keeps the two kernels.
 constexpr int kSampleRecs = 512;        // tap records staged per chunk (as msda_fwd_vec)
 constexpr int kSampleUnroll = 2;
-
-__device__ __forceinline__ float rgroup_max(float v, int G)
-{
-    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float rgroup_add(float v, int G)
-{
-    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // BT: the bank's type, T or fp8e4m3_t (scales [Bv, H*D] applied at the store, as msda_fwd_vec; the ignore-token term
 // stays in T)
@@ -323,7 +345,7 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
     __shared__ LevelLds levels;
     __shared__ float2 stat[QPB];                          // softmax max and 1 / sum per query of the tile
     __shared__ float4 plan[QPB * KC];                     // {x, y, weight} of the chunk's samples
-    constexpr bool kPipe = KC <= 64;                      // live-tap mask + pipelined walk, as in msda_fwd_vec
+    constexpr bool kPipe = KC <= 64;                      // live words + the pipelined walk, as in msda_fwd_vec
     constexpr int QPW = 64 / LPI > 0 ? 64 / LPI : 1;
     __shared__ unsigned long long live[kThreads / 64];
 
@@ -342,20 +364,6 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
     if (kPipe && tid < kThreads / 64) live[tid] = 0ull;
     const float sink_logit = -logf((float)nL);
 
-    // logits of row gl (= image k, level l) of the item (bc.b, sq, bc.h), as plan_forward_kernel forms them
-    auto row_logits = [&](int sq, int gl, float (&lg)[P]) {
-        const int64_t tk = (int64_t)bc.b * pd.Lq + sq;
-        const int k = gl / pd.L, l = gl % pd.L;
-        const int64_t r = relpos[((int64_t)bc.b * pd.Lr + (pd.Lr == 1 ? 0 : sq)) * pd.n + k];
-        float a[P], t[P];
-        load_row<T, P>(att_q + tk * pd.ld_att + (bc.h * pd.L + l) * P, a);
-        load_row<T, P>(att_tab + ((r * pd.H + bc.h) * pd.L + l) * P, t);
-        const float pen = r == 0 ? -10000.f : 0.f;
-#pragma unroll
-        for (int p = 0; p < P; ++p) lg[p] = a[p] + t[p] + pen;
-        return r;
-    };
-
     // ---- softmax statistics of the tile's queries (lane group of G per query, like the plan kernel)
     for (int base = 0; base < QPB * G; base += kThreads) {
         if (base + (tid & ~63) >= QPB * G) continue;      // (whole waves only: the groups shuffle)
@@ -363,24 +371,9 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
         const int sq = bc.q0 + rq;
         const bool item_ok = rq < QPB && sq < d.Nq;
         const bool act = item_ok && gl < nL;
-        float lg[P];
-        float m = sink_logit;
-        if (act) {
-            row_logits(sq, gl, lg);
-#pragma unroll
-            for (int p = 0; p < P; ++p) m = fmaxf(m, lg[p]);
-        } else {
-#pragma unroll
-            for (int p = 0; p < P; ++p) lg[p] = -INFINITY;
-        }
-        m = rgroup_max(m, G);
-        float z = act ? __expf(sink_logit - m) : 0.f;
-        const float my_sink = z;
-#pragma unroll
-        for (int p = 0; p < P; ++p) { lg[p] = __expf(lg[p] - m); z += lg[p]; }
-        z = rgroup_add(z, G);
-        const float inv = 1.f / z;
-        const float sink_sum = rgroup_add(my_sink, G) * inv;
+        float lg[P], m, inv, sink_sum;
+        if (act) row_logits<T, P>(att_q, att_tab, relpos, pd, bc.b, sq, bc.h, gl, lg);
+        sink_softmax<P>(lg, act, sink_logit, LaneGroupRt{G}, m, inv, sink_sum);
         if (item_ok && gl == 0) {
             stat[rq] = make_float2(m, inv);
             ssum[rq] = sink_sum;
@@ -408,26 +401,19 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
                 for (int p = 0; p < P; ++p) dst[p] = make_float4(-8.f, -8.f, 0.f, 0.f);      // outside every map, weight 0
                 continue;
             }
-            float lg[P];
-            const int64_t r = row_logits(sq, gl, lg);
+            float lg[P], oq[2 * P], ot[2 * P], rx, ry, sx, sy;
+            const int64_t r = row_logits<T, P>(att_q, att_tab, relpos, pd, bc.b, sq, bc.h, gl, lg);
             const float2 st2 = stat[rq];
-            const int l = gl % pd.L;
-            float oq[2 * P], ot[2 * P];
-            load_row<T, 2 * P>(off_q + ((int64_t)bc.b * pd.Lq + sq) * pd.ld_off + bc.h * 2 * P, oq);
-            load_row<T, 2 * P>(off_tab + (r * pd.H + bc.h) * 2 * P, ot);
-            const float rx = ref[((int64_t)(pd.Nr == 1 ? 0 : bc.b) * pd.Lq + sq) * 2];
-            const float ry = ref[((int64_t)(pd.Nr == 1 ? 0 : bc.b) * pd.Lq + sq) * 2 + 1];
+#pragma unroll
+            for (int p = 0; p < P; ++p) lg[p] = __expf(lg[p] - st2.x);
             int Hl, Wl, lstart;
             levels.get(shapes, start, gl, Hl, Wl, lstart);
-            const float sx = ratios[l] / (float)Wl, sy = ratios[l] / (float)Hl;
+            row_geometry<T, P>(off_q, off_tab, ref, ratios, pd, bc.b, sq, bc.h, gl, r, (float)Hl, (float)Wl, oq, ot, rx, ry, sx, sy);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                float wgt = __expf(lg[p] - st2.x);
-                wgt *= st2.y;
-                // (as plan_forward_kernel: fp32 results behind an opaque register, then rounded to the storage type)
-                float lx = fmaf(oq[2 * p] + ot[2 * p], sx, rx), ly = fmaf(oq[2 * p + 1] + ot[2 * p + 1], sy, ry);
-                asm volatile("" : "+v"(lx), "+v"(ly), "+v"(wgt));
-                dst[p] = make_float4(to_f32((T)lx), to_f32((T)ly), to_f32((T)wgt), 0.f);
+                float x, y;
+                point_location<T, P>(oq, ot, p, rx, ry, sx, sy, x, y);
+                dst[p] = make_float4(x, y, point_weight<T>(lg[p], st2.y), 0.f);
             }
         }
         __syncthreads();
@@ -435,124 +421,24 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
         for (int r = tid; r < QPB * kc; r += kThreads) {
             const int rq = r / kc, kk = r - rq * kc, gl = (k0 + kk) / P;
             const float4 pl = plan[rq * KC + kk];
-            const float a = pl.z;
             int Hl, Wl, lstart;
             levels.get(shapes, start, gl, Hl, Wl, lstart);
-            const Tap<float> t = locate<float>(pl.x, pl.y, Hl, Wl, lstart);
-            const float gy = 1.f - t.fy, gx = 1.f - t.fx;
-            uint32_t off[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                off[c] = (a != 0.f && t.row[c] >= 0) ? (uint32_t)t.row[c] * row_bytes : kOobOffset;
+            uint4 rows4, ww;
+            tap_record(pl.x, pl.y, pl.z, Hl, Wl, lstart, row_bytes, rows4, ww);
             uint4 *dst = &lds[rq * STRIDE + 2 * kk];
-            const uint4 ww = make_uint4(__float_as_uint(gy * gx * a), __float_as_uint(gy * t.fx * a),
-                                        __float_as_uint(t.fy * gx * a), __float_as_uint(t.fy * t.fx * a));
-            dst[0] = make_uint4(off[0], off[1], off[2], off[3]);
+            dst[0] = rows4;
             dst[1] = ww;
-            if (kPipe && ((ww.x | ww.y | ww.z | ww.w) << 1) != 0u) atomicOr(&live[rq / QPW], 1ull << kk);
+            if (kPipe) mark_live<QPW>(live, rq, kk, ww);
         }
         __syncthreads();
-        if (kPipe) {
-            const int wv = tid >> 6;
-            const unsigned long long mraw = live[wv];
-            unsigned long long m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mraw >> 32)) << 32) |
-                                   (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)mraw);
-            if ((tid & 63) == 0) live[wv] = 0ull;
-            const uint4 *recs = &lds[qi * STRIDE];
-            uint4 rawA[4], rawB[4], wA, wB;
-            auto issue = [&](uint4 (&raw)[4], uint4 &wq) {
-                const int kk = __builtin_ctzll(m);
-                m &= m - 1ull;
-                const uint4 rr = recs[2 * kk];
-                wq = recs[2 * kk + 1];
-                raw[0] = buffer_load16(rsrc, rr.x + lane_off);
-                raw[1] = buffer_load16(rsrc, rr.y + lane_off);
-                raw[2] = buffer_load16(rsrc, rr.z + lane_off);
-                raw[3] = buffer_load16(rsrc, rr.w + lane_off);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            auto consume = [&](const uint4 (&raw)[4], const uint4 &wq) {
-                const float w4[4] = {__uint_as_float(wq.x), __uint_as_float(wq.y), __uint_as_float(wq.z), __uint_as_float(wq.w)};
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float v[VEC];
-                    V::unpack(raw[c], v);
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w4[c], v[i], acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) asm volatile("" : "+v"(acc[i]));
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            const int n_live = __builtin_popcountll(m);
-            if (n_live & 1) { issue(rawA, wA); consume(rawA, wA); }
-            if (n_live >= 2) {
-                issue(rawA, wA);
-                for (int i = 2; i < n_live - 1; i += 2) {
-                    issue(rawB, wB);
-                    consume(rawA, wA);
-                    issue(rawA, wA);
-                    consume(rawB, wB);
-                }
-                issue(rawB, wB);
-                consume(rawA, wA);
-                consume(rawB, wB);
-            }
-        } else
-        // ---- gather (as msda_fwd_vec: 2 taps = 8 row reads in flight per lane, whole-wave skip of zero weights)
-        if (q_ok) {
-            const uint4 *recs = &lds[qi * STRIDE];
-            for (int kk = 0; kk < kc; kk += kSampleUnroll) {
-                uint4 raw[kSampleUnroll][4];
-                float w[kSampleUnroll][4];
-                uint4 rrs[kSampleUnroll];
-                uint32_t any_w = 0u;
-#pragma unroll
-                for (int u = 0; u < kSampleUnroll; ++u) {
-                    rrs[u] = recs[2 * (kk + u)];
-                    const uint4 ww = recs[2 * (kk + u) + 1];
-                    any_w |= (ww.x | ww.y | ww.z | ww.w) << 1;
-                    w[u][0] = __uint_as_float(ww.x); w[u][1] = __uint_as_float(ww.y);
-                    w[u][2] = __uint_as_float(ww.z); w[u][3] = __uint_as_float(ww.w);
-                }
-                if (__builtin_amdgcn_ballot_w64(any_w != 0u) == 0ull) continue;
-#pragma unroll
-                for (int u = 0; u < kSampleUnroll; ++u) {
-                    raw[u][0] = buffer_load16(rsrc, rrs[u].x + lane_off);
-                    raw[u][1] = buffer_load16(rsrc, rrs[u].y + lane_off);
-                    raw[u][2] = buffer_load16(rsrc, rrs[u].z + lane_off);
-                    raw[u][3] = buffer_load16(rsrc, rrs[u].w + lane_off);
-                }
-#pragma unroll
-                for (int u = 0; u < kSampleUnroll; ++u)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float v[VEC];
-                        V::unpack(raw[u][c], v);
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w[u][c], v[i], acc[i]);
-                    }
-            }
-        }
+        // ---- gather (msda_gather.h, as msda_fwd_vec)
+        if (kPipe) gather_live<V>(take_live(live, tid), &lds[qi * STRIDE], rsrc, lane_off, acc);
+        else if (q_ok) gather_all<V, kSampleUnroll>(&lds[qi * STRIDE], kc, rsrc, lane_off, acc);
     }
     if (q_ok) {
         T *o = out + (((int64_t)bc.b * d.Nq + q) * d.H + bc.h) * d.D + lig * VEC;
         apply_scale<BT, VEC>(acc, vscale, (int64_t)value_row(d, bc.b) * HD + (int64_t)bc.h * d.D + lig * VEC);
-        if (token != nullptr) {
-            // the sinks' share goes to the ignore token (mmfs.py:236-241, 274): out + token * sink, with the framework
-            // statement's roundings -- sampled output, sink weight and product each rounded to the storage type first
-            const float sw = to_f32((T)ssum[qi]);
-            float tk[VEC];
-            load_vec<T, VEC>(token + (int64_t)bc.h * d.D + lig * VEC, tk);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                // (two roundings, as the framework's two kernels: the product must not be contracted into the sum --
-                // __fmul_rn / __fadd_rn do not stop this compiler, an opaque register does)
-                float prod = tk[i] * sw;
-                asm volatile("" : "+v"(prod));
-                acc[i] = to_f32((T)acc[i]) + to_f32((T)prod);
-            }
-        }
+        if (token != nullptr) add_ignore_token<T, VEC>(acc, token + (int64_t)bc.h * d.D + lig * VEC, ssum[qi]);
         store_vec<T, VEC, false>(o, acc);
     }
 }
@@ -563,8 +449,8 @@ mmfs_sample_fwd(const BT *__restrict__ value, const int64_t *__restrict__ shapes
 // plan, barrier, tap records, barrier, and then the query's 24 samples two at a time -- a dozen dependent round trips,
 // 13.9 us per call for 4 tokens (profiles/r03by_decode_kernel_stats.csv; 64-lane workgroups of the
 // same kernel: 13.6, r04w).  Here a 64-lane workgroup (one wave: its barriers are free) owns ONE query:
-//   A  lane gl < n*L evaluates row gl of the plan ONCE (logits, softmax over the lane group, locations) -- the
-//      arithmetic, lane groups and reduction order of plan_forward_kernel, so locations and weights are the same bits;
+//   A  lane gl < n*L evaluates row gl of the plan ONCE (logits, softmax over the lane group, locations) -- with the
+//      plan row's functions above, so locations and weights are the same bits;
 //   B  lane s evaluates sample s's tap record from A's row (LDS);
 //   C  the 64 / LPI lane groups take the samples round-robin, EVERY row load of the query in flight at once, and add
 //      their partial sums up in a fixed tree.
@@ -598,55 +484,27 @@ mmfs_sample_decode(const BT *__restrict__ value, const int64_t *__restrict__ sha
     const BT *slab = value + ((int64_t)value_row(d, b) * d.S) * HD + (int64_t)h * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(BT));
     const __amdgpu_buffer_rsrc_t rsrc = make_slab_rsrc(slab, ((int64_t)d.S * HD - (int64_t)h * d.D) * (int64_t)sizeof(BT));
-    const float sink_logit = -logf((float)nL);
-    const int64_t tk = (int64_t)b * pd.Lq + q;
 
     // ---- A: row gl of the plan (lanes of the first lane group; the others idle through the shuffles)
     float sink_sum;
     {
         const int gl = tid;
         const bool act = gl < nL;
-        float lg[P], oq[2 * P], ot[2 * P];
-        float m = sink_logit, rx = 0.f, ry = 0.f, sx = 0.f, sy = 0.f;
+        float lg[P], oq[2 * P], ot[2 * P], m, inv, rx, ry, sx, sy;
         if (act) {
-            const int k = gl / pd.L, l = gl % pd.L;
-            const int64_t r = relpos[((int64_t)b * pd.Lr + (pd.Lr == 1 ? 0 : q)) * pd.n + k];
-            float a[P], t[P];
-            load_row<T, P>(att_q + tk * pd.ld_att + (h * pd.L + l) * P, a);
-            load_row<T, 2 * P>(off_q + tk * pd.ld_off + h * 2 * P, oq);
-            rx = ref[((int64_t)(pd.Nr == 1 ? 0 : b) * pd.Lq + q) * 2];
-            ry = ref[((int64_t)(pd.Nr == 1 ? 0 : b) * pd.Lq + q) * 2 + 1];
+            const int64_t r = row_logits<T, P>(att_q, att_tab, relpos, pd, b, q, h, gl, lg);
             const int Hl = (int)shapes[2 * gl], Wl = (int)shapes[2 * gl + 1];
             rowinfo[3 * gl] = Hl; rowinfo[3 * gl + 1] = Wl; rowinfo[3 * gl + 2] = (int)start[gl];
-            sx = ratios[l] / (float)Wl; sy = ratios[l] / (float)Hl;
-            load_row<T, P>(att_tab + ((r * pd.H + h) * pd.L + l) * P, t);
-            load_row<T, 2 * P>(off_tab + (r * pd.H + h) * 2 * P, ot);
-            const float pen = r == 0 ? -10000.f : 0.f;
-#pragma unroll
-            for (int p = 0; p < P; ++p) { lg[p] = a[p] + t[p] + pen; m = fmaxf(m, lg[p]); }
-        } else {
-#pragma unroll
-            for (int p = 0; p < P; ++p) lg[p] = -INFINITY;
-#pragma unroll
-            for (int p = 0; p < 2 * P; ++p) { oq[p] = 0.f; ot[p] = 0.f; }
+            row_geometry<T, P>(off_q, off_tab, ref, ratios, pd, b, q, h, gl, r, (float)Hl, (float)Wl, oq, ot, rx, ry, sx, sy);
         }
-        m = rgroup_max(m, G);
-        float z = act ? __expf(sink_logit - m) : 0.f;
-        const float my_sink = z;
-#pragma unroll
-        for (int p = 0; p < P; ++p) { lg[p] = __expf(lg[p] - m); z += lg[p]; }
-        z = rgroup_add(z, G);
-        const float inv = 1.f / z;
-        sink_sum = rgroup_add(my_sink, G) * inv;
-        if (tid == 0 && sink != nullptr) sink[tk * pd.H + h] = sink_sum;
+        sink_softmax<P>(lg, act, -logf((float)nL), LaneGroupRt{G}, m, inv, sink_sum);
+        if (tid == 0 && sink != nullptr) sink[((int64_t)b * pd.Lq + q) * pd.H + h] = sink_sum;
         if (act) {
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                float wgt = lg[p] * inv;
-                // (as plan_forward_kernel: fp32 results behind an opaque register, then rounded to the storage type)
-                float lx = fmaf(oq[2 * p] + ot[2 * p], sx, rx), ly = fmaf(oq[2 * p + 1] + ot[2 * p + 1], sy, ry);
-                asm volatile("" : "+v"(lx), "+v"(ly), "+v"(wgt));
-                plan[gl * P + p] = make_float4(to_f32((T)lx), to_f32((T)ly), to_f32((T)wgt), 0.f);
+                float x, y;
+                point_location<T, P>(oq, ot, p, rx, ry, sx, sy, x, y);
+                plan[gl * P + p] = make_float4(x, y, point_weight<T>(lg[p], inv), 0.f);
             }
         }
     }
@@ -656,16 +514,10 @@ mmfs_sample_decode(const BT *__restrict__ value, const int64_t *__restrict__ sha
     for (int s = tid; s < d.K; s += 64) {
         const int gl = s / P;
         const float4 pl = plan[s];
-        const float a = pl.z;
-        const Tap<float> t = locate<float>(pl.x, pl.y, rowinfo[3 * gl], rowinfo[3 * gl + 1], rowinfo[3 * gl + 2]);
-        const float gy = 1.f - t.fy, gx = 1.f - t.fx;
-        uint32_t off[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            off[c] = (a != 0.f && t.row[c] >= 0) ? (uint32_t)t.row[c] * row_bytes : kOobOffset;
-        recs[2 * s] = make_uint4(off[0], off[1], off[2], off[3]);
-        recs[2 * s + 1] = make_uint4(__float_as_uint(gy * gx * a), __float_as_uint(gy * t.fx * a),
-                                     __float_as_uint(t.fy * gx * a), __float_as_uint(t.fy * t.fx * a));
+        uint4 rows, ww;
+        tap_record(pl.x, pl.y, pl.z, rowinfo[3 * gl], rowinfo[3 * gl + 1], rowinfo[3 * gl + 2], row_bytes, rows, ww);
+        recs[2 * s] = rows;
+        recs[2 * s + 1] = ww;
     }
     __syncthreads();
     // ---- C: lane group `sub` takes samples sub, sub + NSUB, ...; a batch's row loads all leave before the first is used
@@ -679,25 +531,13 @@ mmfs_sample_decode(const BT *__restrict__ value, const int64_t *__restrict__ sha
 #pragma unroll
         for (int u = 0; u < kDecodeBatch; ++u) {
             const int kk = k0 + u * NSUB + sub;
-            uint4 rr = make_uint4(kOobOffset, kOobOffset, kOobOffset, kOobOffset);
-            wq[u] = make_uint4(0u, 0u, 0u, 0u);
+            uint4 rr;
+            tap_record_none(rr, wq[u]);
             if (kk < d.K) { rr = recs[2 * kk]; wq[u] = recs[2 * kk + 1]; }
-            raw[u][0] = buffer_load16(rsrc, rr.x + lane_off);
-            raw[u][1] = buffer_load16(rsrc, rr.y + lane_off);
-            raw[u][2] = buffer_load16(rsrc, rr.z + lane_off);
-            raw[u][3] = buffer_load16(rsrc, rr.w + lane_off);
+            load_rows(rsrc, rr, lane_off, raw[u]);
         }
 #pragma unroll
-        for (int u = 0; u < kDecodeBatch; ++u) {
-            const float w4[4] = {__uint_as_float(wq[u].x), __uint_as_float(wq[u].y), __uint_as_float(wq[u].z), __uint_as_float(wq[u].w)};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float v[VEC];
-                V::unpack(raw[u][c], v);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w4[c], v[i], acc[i]);
-            }
-        }
+        for (int u = 0; u < kDecodeBatch; ++u) fma_rows<V>(raw[u], wq[u], acc);
     }
 #pragma unroll
     for (int o = 32; o >= LPI; o >>= 1)
@@ -706,18 +546,7 @@ mmfs_sample_decode(const BT *__restrict__ value, const int64_t *__restrict__ sha
     if (sub == 0) {
         T *o = out + (((int64_t)b * d.Nq + q) * d.H + h) * d.D + lig * VEC;
         apply_scale<BT, VEC>(acc, vscale, (int64_t)value_row(d, b) * HD + (int64_t)h * d.D + lig * VEC);
-        if (token != nullptr) {
-            // (mmfs_sample_fwd's statement of the ignore-token term: sampled output, sink weight and product each rounded first)
-            const float sw = to_f32((T)sink_sum);
-            float tkn[VEC];
-            load_vec<T, VEC>(token + (int64_t)h * d.D + lig * VEC, tkn);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float prod = tkn[i] * sw;
-                asm volatile("" : "+v"(prod));
-                acc[i] = to_f32((T)acc[i]) + to_f32((T)prod);
-            }
-        }
+        if (token != nullptr) add_ignore_token<T, VEC>(acc, token + (int64_t)h * d.D + lig * VEC, sink_sum);
         store_vec<T, VEC, false>(o, acc);
     }
 }
@@ -729,8 +558,6 @@ int sample_groups(int64_t Lq, int64_t K, int64_t nL, int lpi)
     if ((e && e[0] == '0') || Lq > kDecodeMaxQ || K > kDecodeMaxK || nL > 64 || lpi > 32) return 1;
     return 64 / lpi;
 }
-
-int esize(int dtype) { return dtype == MMFS_F32 ? 4 : (dtype == MMFS_F16 || dtype == MMFS_BF16) ? 2 : 0; }
 
 int check_dims(int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P, int64_t n, int64_t M, int64_t Lr,
                int64_t Nr, PlanDims *d)
@@ -764,16 +591,6 @@ static int for_group(int nL, F &&f)
 
 extern "C" {
 
-// rows `ld` elements apart (0 = packed, `cols`), vector accesses of `vec` elements of `es` bytes: dimensions and alignment
-static int heads_rows(int64_t &ld, int64_t cols, const void *p, int64_t vec, int64_t es)
-{
-    if (ld == 0) ld = cols;
-    if (ld < cols || ld > 0x7fffffffLL) return MMFS_E_DIMS;
-    const int64_t a = vec * es < 16 ? vec * es : 16;                   // (load_row / store_row: accesses of at most 16 bytes)
-    if ((ld * es) % a || (uintptr_t)p % (uintptr_t)a) return MMFS_E_ALIGN;
-    return MMFS_OK;
-}
-
 int mmfs_plan_forward(int dtype, const void *off_q, const void *att_q, const void *off_tab,
                       const void *att_tab, const int64_t *relpos, const float *ref,
                       const int64_t *shapes, const float *ratios, void *loc, void *attn, float *sink,
@@ -792,7 +609,7 @@ int mmfs_plan_forward_heads(int dtype, const void *off_q, const void *att_q, int
                             int64_t Lr, int64_t Nr, void *stream)
 {
     using namespace mmfs;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     PlanDims d;
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &d);
@@ -824,9 +641,7 @@ int mmfs_plan_forward_heads(int dtype, const void *off_q, const void *att_q, int
         if (P == 8) return go(tag_t, std::integral_constant<int, 8>());
         return go(tag_t, std::integral_constant<int, 16>());
     };
-    if (dtype == MMFS_F32) return by_p(float());
-    if (dtype == MMFS_F16) return by_p(half_t());
-    return by_p(bf16_t());
+    return by_type(dtype, by_p);
 }
 
 int mmfs_plan_backward(int dtype, const void *grad_loc, const void *grad_attn, const float *grad_sink,
@@ -849,7 +664,7 @@ int mmfs_plan_backward_heads(int dtype, const void *grad_loc, const void *grad_a
                              int64_t Lr, int64_t Nr, void *stream)
 {
     using namespace mmfs;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     PlanDims d;
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &d);
@@ -888,9 +703,7 @@ int mmfs_plan_backward_heads(int dtype, const void *grad_loc, const void *grad_a
         if (P == 8) return go(tag_t, std::integral_constant<int, 8>());
         return go(tag_t, std::integral_constant<int, 16>());
     };
-    if (dtype == MMFS_F32) return by_p(float());
-    if (dtype == MMFS_F16) return by_p(half_t());
-    return by_p(bf16_t());
+    return by_type(dtype, by_p);
 }
 
 int mmfs_sample_forward(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
@@ -970,7 +783,7 @@ static int sample_forward_any(int dtype, bool fp8, const void *value, const floa
                               int64_t P, int64_t n, int64_t M, int64_t Lr, int64_t Nr, void *stream)
 {
     using namespace mmfs;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     const int bes = fp8 ? 1 : es;                                           // the bank's element size
     PlanDims pd;
@@ -1067,14 +880,12 @@ static int sample_forward_any(int dtype, bool fp8, const void *value, const floa
             default: return by_p(tag_t, b, std::integral_constant<int, 64>());
         }
     };
-    if (dtype == MMFS_F32) return by_lpi(float());
-    if (dtype == MMFS_F16) return by_lpi(half_t());
-    return by_lpi(bf16_t());
+    return by_type(dtype, by_lpi);
 }
 
 int mmfs_sample_forward_groups(int dtype, int64_t Lq, int64_t D, int64_t nL, int64_t P)
 {
-    const int es = mmfs::esize(dtype);
+    const int es = mmfs::elem_size(dtype);
     if (!es || D <= 0 || D % (16 / es) || (P != 4 && P != 8) || nL <= 0 || Lq <= 0) return 0;
     const int64_t lpi = D / (16 / es);
     if (lpi > 64 || (lpi & (lpi - 1))) return 0;

@@ -36,8 +36,7 @@
 //
 // The extents reach the kernels by value (Pyr): no device table, no allocation, no synchronisation -- the launches can
 // be captured into a graph.  Offsets are 64-bit.
-#include "../../include/mmfs_msda.h"
-#include "msda_device.h"
+#include "msda_host.h"
 #include <hip/hip_runtime.h>
 
 namespace mmfs {
@@ -285,10 +284,6 @@ pyramid_bwd_rows(const T *__restrict__ gr, T *__restrict__ g_up, T *__restrict__
 }
 
 // ---------------------------------------------------------------- backward, g_c1 in NCHW: level 1's gradient rows transposed (bits only)
-template <int BYTES> struct Word;
-template <> struct Word<2> { typedef uint16_t type; };
-template <> struct Word<4> { typedef uint32_t type; };
-
 template <int BYTES>
 __global__ void __launch_bounds__(kThreads)
 pyramid_bwd_c1_nchw(const void *__restrict__ gr_, void *__restrict__ g_c1_, const Pyr g, const int C, const int c_tiles,
@@ -327,8 +322,6 @@ pyramid_bwd_c1_nchw(const void *__restrict__ gr_, void *__restrict__ g_c1_, cons
     }
 }
 
-int esize(int dtype) { return dtype == MMFS_F32 ? 4 : (dtype == MMFS_F16 || dtype == MMFS_BF16) ? 2 : 0; }
-
 bool supported(int es, int64_t C, int64_t H, int64_t W, int levels)
 {
     return es && C >= 0 && (C * es) % 16 == 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && levels >= 1 && levels <= 15;
@@ -357,7 +350,7 @@ void lay_out_backward(Plan *p, int64_t B, const bool (&seg_on)[5])
 // the checks every entry shares, in the header's order; MMFS_OK with plan->empty set for B * C == 0
 int make_plan(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int levels, int c1_layout, Plan *p)
 {
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     if (B < 0 || H < 0 || W < 0 || C < 0) return MMFS_E_DIMS;
     if (!supported(es, C, H, W, levels) || (c1_layout != MMFS_PYRAMID_C1_NCHW && c1_layout != MMFS_PYRAMID_C1_NHWC))
@@ -395,13 +388,6 @@ int make_plan(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int levels,
     return MMFS_OK;
 }
 
-template <typename F> int by_type(int dtype, F &&f)
-{
-    if (dtype == MMFS_F32) return f(float());
-    if (dtype == MMFS_F16) return f(half_t());
-    return f(bf16_t());
-}
-
 }  // namespace
 }  // namespace mmfs
 
@@ -409,7 +395,7 @@ extern "C" {
 
 int mmfs_pyramid_head_supported(int dtype, int64_t C, int64_t H, int64_t W, int levels)
 {
-    return mmfs::supported(mmfs::esize(dtype), C, H, W, levels);
+    return mmfs::supported(mmfs::elem_size(dtype), C, H, W, levels);
 }
 
 int mmfs_pyramid_head_forward(int dtype, const void *c, const void *x1, const void *x2, const void *x3, const void *x4,
@@ -472,7 +458,7 @@ int mmfs_pyramid_head_backward(int dtype, const void *grad_out, void *grad_up, v
     const bool seg_on[5] = {grad_up || rows_c1, gx[0] != nullptr, gx[1] != nullptr, gx[2] != nullptr, gx[3] != nullptr};
     lay_out_backward(&p, B, seg_on);
     const bool tile = grad_c1 && !rows1;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     return by_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         if (p.bwd_total) {

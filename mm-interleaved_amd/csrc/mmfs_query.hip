@@ -26,13 +26,6 @@ namespace {
 constexpr int kQueryThreads = 256;
 constexpr int kQueryPad = 8;                  // elements: rows of the tile stay 16-byte aligned
 
-__device__ __forceinline__ float qwave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // The tile: pixel p's channels as 16-byte vectors, vector v at slot v ^ ((p >> 3) & 7) of row p.  A lane that moves
 // 8 pixels of one channel touches 8 rows of one column; the lanes of a wave differ in the pixel octet (p >> 3) and
 // in the channel -- the swizzle puts the octets on different banks (row pitch = 32 k + 4 words).
@@ -115,7 +108,7 @@ query_prep(const T *__restrict__ x, const T *__restrict__ gamma, const T *__rest
                 for (int j = 0; j < 8; ++j) s += f[i][j];
             }
         }
-        const float mean = qwave_sum(s) * inv_c;
+        const float mean = wave_sum(s) * inv_c;
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -124,7 +117,7 @@ query_prep(const T *__restrict__ x, const T *__restrict__ gamma, const T *__rest
                 for (int j = 0; j < 8; ++j) { const float d = f[i][j] - mean; ss = fmaf(d, d, ss); }
             }
         }
-        const float rstd = rsqrtf(qwave_sum(ss) * inv_c + eps);
+        const float rstd = rsqrtf(wave_sum(ss) * inv_c + eps);
         if (lane == 0 && mean_out != nullptr) { mean_out[tok] = mean; rstd_out[tok] = rstd; }
         uint4 *qr = reinterpret_cast<uint4 *>(q + tok * C);
 #pragma unroll

@@ -1,8 +1,8 @@
 // msda_capi.hip -- the extern "C" surface declared in include/mmfs_msda.h.
 // Validates arguments, narrows the dims to the kernels' 32-bit index range and
 // forwards to the kernel launchers.  No state, no allocation.
-#include "../../include/mmfs_msda.h"
 #include "msda_env.h"
+#include "msda_host.h"
 #include "msda_launch.h"
 #include "msda_plan.h"
 #include <cstring>
@@ -10,15 +10,8 @@
 
 namespace {
 
-int elem_size(int dtype)
-{
-    switch (dtype) {
-        case MMFS_F32: return 4;
-        case MMFS_F16: case MMFS_BF16: return 2;
-        case MMFS_F64: return 8;
-        default: return 0;
-    }
-}
+// the op alone serves fp64
+int elem_size(int dtype) { return mmfs::elem_size(dtype, true); }
 
 // Fills d; returns MMFS_OK, or an error.  *empty is set when there is nothing to launch.
 int make_dims(int64_t B, int64_t S, int64_t H, int64_t D, int64_t L, int64_t Nq, int64_t P,

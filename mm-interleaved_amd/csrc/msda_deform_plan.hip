@@ -18,9 +18,10 @@
 //
 // deform_sample_fwd is msda_fwd_vec (csrc/msda_fwd.hip) with its staging replaced, as mmfs_sample_fwd is for MMFS:
 // the workgroup evaluates the plan of its 256 / LPI queries with the SAME device functions, lane groups and
-// reduction order as deform_plan_fwd, rounds locations and weights to T, and turns them into tap records in LDS.
-#include "../../include/mmfs_msda.h"
-#include "msda_device.h"
+// reduction order as deform_plan_fwd, rounds locations and weights to T, and turns them into tap records in LDS, which
+// it walks with msda_fwd_vec's own functions (msda_gather.h).
+#include "msda_gather.h"
+#include "msda_host.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <type_traits>
@@ -38,33 +39,6 @@ struct DeformDims {
     int G;                  // lane-group width: the power of two >= L
     int ld_off, ld_att;     // elements between two tokens' rows of off / logit (H*L*P*2, H*L*P when packed)
 };
-
-__device__ __forceinline__ float group_max(float v, int G)
-{
-    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float group_add(float v, int G)
-{
-    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// P elements of T <-> floats, as one aligned vector access (at most 16 bytes at a time)
-template <typename T, int P> __device__ __forceinline__ void load_row(const T *p, float (&o)[P])
-{
-    T tmp[P];
-    __builtin_memcpy(tmp, __builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), P * sizeof(T));
-#pragma unroll
-    for (int i = 0; i < P; ++i) o[i] = to_f32(tmp[i]);
-}
-template <typename T, int P> __device__ __forceinline__ void store_row(T *p, const float (&v)[P])
-{
-    T tmp[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) tmp[i] = (T)v[i];
-    __builtin_memcpy(__builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), tmp, P * sizeof(T));
-}
 
 // reference point and offset scale of (sample nb, query q, level l):  loc = ref + off * scale
 __device__ __forceinline__ void row_geometry(const float *__restrict__ ref, const DeformDims &d, int nb, int q, int l,
@@ -252,11 +226,10 @@ deform_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shape
             const int sq = bc.q0 + rq;
             uint4 *dst = &lds[rq * STRIDE + 2 * rr * P];
             if (sq >= d.Nq) {
+                uint4 rows, ww;
+                tap_record_none(rows, ww);
 #pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    dst[2 * p] = make_uint4(kOobOffset, kOobOffset, kOobOffset, kOobOffset);
-                    dst[2 * p + 1] = make_uint4(0u, 0u, 0u, 0u);
-                }
+                for (int p = 0; p < P; ++p) { dst[2 * p] = rows; dst[2 * p + 1] = ww; }
                 continue;
             }
             const int64_t tk = (int64_t)bc.b * pd.Lq + sq;
@@ -269,67 +242,15 @@ deform_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shape
             row_values<T, P>(lg, st2.x, st2.y, of, rx, ry, sx, sy, w, xy);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                const float a = w[p];
-                const Tap<float> t = locate<float>(xy[2 * p], xy[2 * p + 1], Hl, Wl, lstart);
-                const float gy = 1.f - t.fy, gx = 1.f - t.fx;
-                uint32_t o4[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    o4[c] = (a != 0.f && t.row[c] >= 0) ? (uint32_t)t.row[c] * row_bytes : kOobOffset;
-                const uint4 ww = make_uint4(__float_as_uint(gy * gx * a), __float_as_uint(gy * t.fx * a),
-                                            __float_as_uint(t.fy * gx * a), __float_as_uint(t.fy * t.fx * a));
-                dst[2 * p] = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+                uint4 rows, ww;
+                tap_record(xy[2 * p], xy[2 * p + 1], w[p], Hl, Wl, lstart, row_bytes, rows, ww);
+                dst[2 * p] = rows;
                 dst[2 * p + 1] = ww;
-                if (((ww.x | ww.y | ww.z | ww.w) << 1) != 0u) atomicOr(&live[rq / QPW], 1ull << (rr * P + p));
+                mark_live<QPW>(live, rq, rr * P + p, ww);
             }
         }
         __syncthreads();
-        // ---- gather, software-pipelined over the live samples (msda_fwd_vec's walk)
-        const int wv = tid >> 6;
-        const unsigned long long mraw = live[wv];
-        unsigned long long m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mraw >> 32)) << 32) |
-                               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)mraw);
-        if ((tid & 63) == 0) live[wv] = 0ull;               // (mine; the next chunk's staging sets it after the barrier)
-        const uint4 *recs = &lds[qi * STRIDE];
-        uint4 rawA[4], rawB[4], wA, wB;
-        auto issue = [&](uint4 (&raw)[4], uint4 &wq) {
-            const int kk = __builtin_ctzll(m);
-            m &= m - 1ull;
-            const uint4 rr = recs[2 * kk];
-            wq = recs[2 * kk + 1];
-            raw[0] = buffer_load16(rsrc, rr.x + lane_off);
-            raw[1] = buffer_load16(rsrc, rr.y + lane_off);
-            raw[2] = buffer_load16(rsrc, rr.z + lane_off);
-            raw[3] = buffer_load16(rsrc, rr.w + lane_off);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        auto consume = [&](const uint4 (&raw)[4], const uint4 &wq) {
-            const float w4[4] = {__uint_as_float(wq.x), __uint_as_float(wq.y), __uint_as_float(wq.z), __uint_as_float(wq.w)};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float v[VEC];
-                V::unpack(raw[c], v);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w4[c], v[i], acc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) asm volatile("" : "+v"(acc[i]));
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        const int n_live = __builtin_popcountll(m);
-        if (n_live & 1) { issue(rawA, wA); consume(rawA, wA); }
-        if (n_live >= 2) {
-            issue(rawA, wA);
-            for (int i = 2; i < n_live - 1; i += 2) {
-                issue(rawB, wB);
-                consume(rawA, wA);
-                issue(rawA, wA);
-                consume(rawB, wB);
-            }
-            issue(rawB, wB);
-            consume(rawA, wA);
-            consume(rawB, wB);
-        }
+        gather_live<V>(take_live(live, tid), &lds[qi * STRIDE], rsrc, lane_off, acc);
     }
     if (q_ok) {
         T *o = out + (((int64_t)bc.b * d.Nq + q) * d.H + bc.h) * d.D + lig * VEC;
@@ -337,14 +258,12 @@ deform_sample_fwd(const T *__restrict__ value, const int64_t *__restrict__ shape
     }
 }
 
-int esize(int dtype) { return dtype == MMFS_F32 ? 4 : (dtype == MMFS_F16 || dtype == MMFS_BF16) ? 2 : 0; }
-
 // dtype / dimension checks shared by the three entries (MMFS_OK: ``d`` is filled, leading dimensions packed)
 int check_dims(int dtype, int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P, int64_t Nr, int64_t Lref, int64_t R,
                DeformDims *d)
 {
     const int64_t lim = 0x7fffffffLL;
-    if (!esize(dtype)) return MMFS_E_DTYPE;
+    if (!elem_size(dtype)) return MMFS_E_DTYPE;
     if (N < 0 || Lq < 0 || H <= 0 || L <= 0 || P <= 0) return MMFS_E_DIMS;
     if (N > lim || Lq > lim || H > lim || N * Lq > lim || N * Lq * H > lim) return MMFS_E_DIMS;
     if ((Nr != 1 && Nr != N) || (Lref != 1 && Lref != L) || (R != 2 && R != 4)) return MMFS_E_DIMS;
@@ -358,26 +277,13 @@ int check_dims(int dtype, int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P
     return MMFS_OK;
 }
 
-// rows ``ld`` elements apart (0 = packed, ``cols``), vector accesses of ``vec`` elements of ``es`` bytes
-int heads_rows(int64_t &ld, int64_t cols, const void *p, int64_t vec, int64_t es)
-{
-    if (ld == 0) ld = cols;
-    if (ld < cols || ld > 0x7fffffffLL) return MMFS_E_DIMS;
-    const int64_t a = vec * es < 16 ? vec * es : 16;
-    if ((ld * es) % a || (uintptr_t)p % (uintptr_t)a) return MMFS_E_ALIGN;
-    return MMFS_OK;
-}
-
 template <typename F> int by_type_and_points(int dtype, int64_t P, F &&f)
 {
-    auto by_p = [&](auto tag_t) {
+    return by_type(dtype, [&](auto tag_t) {
         if (P == 2) return f(tag_t, std::integral_constant<int, 2>());
         if (P == 4) return f(tag_t, std::integral_constant<int, 4>());
         return f(tag_t, std::integral_constant<int, 8>());
-    };
-    if (dtype == MMFS_F32) return by_p(float());
-    if (dtype == MMFS_F16) return by_p(half_t());
-    return by_p(bf16_t());
+    });
 }
 
 // lanes per query of the fused sampler for head rows of D elements, 0 when it does not serve them
@@ -397,7 +303,7 @@ extern "C" {
 int mmfs_deform_plan_supported(int dtype, int64_t L, int64_t P, int64_t R, int64_t D)
 {
     using namespace mmfs;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es || L <= 0 || L > kMaxLevels || (P != 2 && P != 4 && P != 8) || (R != 2 && R != 4)) return 0;
     return 1 | (sampler_lpi(es, D) ? 2 : 0);
 }
@@ -414,7 +320,7 @@ int mmfs_deform_plan_forward(int dtype, const void *off, const void *logit, int6
     const int64_t items = N * Lq * H;
     if (items == 0) return MMFS_OK;
     if (!off || !logit || !ref || !shapes || !loc || !attn) return MMFS_E_NULLPTR;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     int rr;
     if ((rr = heads_rows(ld_off, H * L * P * 2, off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, logit, P, es)))
         return rr;
@@ -444,7 +350,7 @@ int mmfs_deform_plan_backward(int dtype, const void *grad_loc, const void *grad_
     const int64_t items = N * Lq * H;
     if (items == 0) return MMFS_OK;
     if (!grad_loc || !grad_attn || !attn || !ref || !shapes || !grad_off || !grad_logit) return MMFS_E_NULLPTR;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     int rr;
     if ((rr = heads_rows(ld_off, H * L * P * 2, grad_off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, grad_logit, P, es)))
         return rr;
@@ -474,7 +380,7 @@ int mmfs_deform_sample_forward(int dtype, const void *value, const int64_t *shap
     if (rc) return rc;
     if (S < 0 || D <= 0 || S > 0x7ffffffdLL || H * D > 0x7fffffffLL) return MMFS_E_DIMS;
     if (N * Lq * H == 0) return MMFS_OK;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     const int lpi = sampler_lpi(es, D);
     if (!lpi || S == 0 || S * H * D * (int64_t)es > kMaxSlabBytes) return MMFS_E_UNSUPPORTED;
     if (!value || !shapes || !start || !off || !logit || !ref || !out) return MMFS_E_NULLPTR;

@@ -162,6 +162,54 @@ __device__ __forceinline__ void apply_scale(float (&acc)[VEC], const float *__re
     }
 }
 
+// P elements of T <-> floats, as one aligned vector access (P * sizeof(T) is 4 .. 64 bytes: at most 16 at a time)
+template <typename T, int P> __device__ __forceinline__ void load_row(const T *p, float (&o)[P])
+{
+    T tmp[P];
+    __builtin_memcpy(tmp, __builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), P * sizeof(T));
+#pragma unroll
+    for (int i = 0; i < P; ++i) o[i] = to_f32(tmp[i]);
+}
+template <typename T, int P> __device__ __forceinline__ void store_row(T *p, const float (&v)[P])
+{
+    T tmp[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) tmp[i] = (T)v[i];
+    __builtin_memcpy(__builtin_assume_aligned(p, P * sizeof(T) >= 16 ? 16 : P * sizeof(T)), tmp, P * sizeof(T));
+}
+
+// an element of BYTES bytes moved as bits (transposes, copies)
+template <int BYTES> struct Word;
+template <> struct Word<2> { typedef uint16_t type; };
+template <> struct Word<4> { typedef uint32_t type; };
+
+// ---------------------------------------------------------------- reductions by wave shuffles
+// lane group: G = 2^k consecutive lanes of a wave (the plan kernels: one lane per row of P points).  G as a template
+// argument unrolls; both walk the same butterfly, so a kernel of either kind sums in the same order.
+template <int G> __device__ __forceinline__ float group_max(float v)
+{
+#pragma unroll
+    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+template <int G> __device__ __forceinline__ float group_add(float v)
+{
+#pragma unroll
+    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float group_max(float v, int G)
+{
+    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float group_add(float v, int G)
+{
+    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return group_add<64>(v); }
+
 // ---------------------------------------------------------------- bilinear tap
 // One sample's 2x2 footprint.  row[i] is the pixel index inside the whole value
 // tensor's S axis (level start included), or -1 when the corner is outside the map

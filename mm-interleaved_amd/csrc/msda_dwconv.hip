@@ -34,8 +34,7 @@
 //
 // Level extents reach the kernels by value (ConvLevels, at most 8 levels): no device table, no allocation, no
 // synchronisation -- the launches can be captured into a graph.
-#include "../../include/mmfs_msda.h"
-#include "msda_device.h"
+#include "msda_host.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <type_traits>
@@ -344,8 +343,6 @@ dwconv_wgrad_reduce(const float *__restrict__ partial, const int rows, const int
     }
 }
 
-int esize(int dtype) { return dtype == MMFS_F32 ? 4 : (dtype == MMFS_F16 || dtype == MMFS_BF16) ? 2 : 0; }
-
 struct ConvPlan {
     ConvLevels fwd, bwd;
     int CV;                     // 16-byte channel vectors per token (forward lanes)
@@ -375,7 +372,7 @@ int fill_levels(const int64_t *level_hw, int L, int64_t N, int rows, ConvLevels 
 // the checks every entry shares, in the header's order; MMFS_OK with plan->empty set for B * N * C == 0
 int make_plan(int dtype, const int64_t *level_hw, int64_t B, int64_t N, int64_t C, int64_t L, int act, ConvPlan *p)
 {
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     if (!es) return MMFS_E_DTYPE;
     if (B < 0 || N < 0 || C < 0) return MMFS_E_DIMS;
     if (L < 1 || L > kMaxLevels || (C * es) % 16 || (act != MMFS_DWCONV_ACT_NONE && act != MMFS_DWCONV_ACT_GELU))
@@ -401,13 +398,6 @@ int make_plan(int dtype, const int64_t *level_hw, int64_t B, int64_t N, int64_t 
     return MMFS_OK;
 }
 
-template <typename F> int by_type(int dtype, F &&f)
-{
-    if (dtype == MMFS_F32) return f(float());
-    if (dtype == MMFS_F16) return f(half_t());
-    return f(bf16_t());
-}
-
 }  // namespace
 }  // namespace mmfs
 
@@ -416,7 +406,7 @@ extern "C" {
 int mmfs_dwconv_tokens_supported(int dtype, int64_t C, int64_t L, int act)
 {
     using namespace mmfs;
-    const int es = esize(dtype);
+    const int es = elem_size(dtype);
     return es && C >= 0 && (C * es) % 16 == 0 && L >= 1 && L <= kMaxLevels &&
            (act == MMFS_DWCONV_ACT_NONE || act == MMFS_DWCONV_ACT_GELU);
 }
@@ -464,7 +454,7 @@ int mmfs_dwconv_tokens_backward(int dtype, const void *grad_out, const void *x, 
     if (!grad_out || !x || !weight || !grad_x || !grad_weight || !workspace || (act == MMFS_DWCONV_ACT_GELU && !pre))
         return MMFS_E_NULLPTR;
     if (((uintptr_t)grad_out | (uintptr_t)x | (uintptr_t)pre | (uintptr_t)weight | (uintptr_t)grad_x | (uintptr_t)workspace) % 16 ||
-        ((uintptr_t)grad_weight | (uintptr_t)grad_bias) % (uintptr_t)esize(dtype))
+        ((uintptr_t)grad_weight | (uintptr_t)grad_bias) % (uintptr_t)elem_size(dtype))
         return MMFS_E_ALIGN;
     const dim3 grid((unsigned)p.bwd_blocks, (unsigned)((p.CL + p.CLB - 1) / p.CLB));
     const int E = (int)(kSums * C);

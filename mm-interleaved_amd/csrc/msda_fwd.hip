@@ -18,7 +18,7 @@
 //
 // A scalar kernel (one thread per output element) covers head widths that are not
 // 16-byte * power-of-two, and fp64.
-#include "msda_device.h"
+#include "msda_gather.h"
 #include "msda_launch.h"
 
 namespace mmfs {
@@ -30,11 +30,23 @@ constexpr int kRecsPerBlock = 512;      // tap records staged per chunk (16 KiB)
 #endif
 constexpr int kUnroll = MMFS_FWD_UNROLL;   // taps in flight per lane (4x row reads each)
 
-struct alignas(16) FwdRec {
-    int row[4];
-    float w[4];
-};
-
+// The flat-address kernels' tap record (tap_record's, msda_gather.h, with pixel-row indices for byte offsets): -1 for a
+// corner that reads nothing.  Flat addresses have no descriptor to stop a row that a malformed level table puts past S.
+__device__ __forceinline__ void flat_record(float lx, float ly, float a, int Hl, int Wl, int lstart, int S,
+                                            uint4 &rows, uint4 &ww)
+{
+    const Tap<float> t = locate<float>(lx, ly, Hl, Wl, lstart);
+    const float gy = 1.f - t.fy, gx = 1.f - t.fx;
+    int row[4] = {-1, -1, -1, -1};
+    if (a != 0.f) {
+        row[0] = t.row[0]; row[1] = t.row[1]; row[2] = t.row[2]; row[3] = t.row[3];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) row[c] = row[c] < S ? row[c] : -1;
+    rows = make_uint4(row[0], row[1], row[2], row[3]);
+    ww = make_uint4(__float_as_uint(gy * gx * a), __float_as_uint(gy * t.fx * a),
+                    __float_as_uint(t.fy * gx * a), __float_as_uint(t.fy * t.fx * a));
+}
 // BUF = true : row reads through a buffer descriptor (32-bit offsets, hardware zero for
 //              corners outside the map)               -- slabs < 2 GiB, the normal case
 // BUF = false: 64-bit flat addresses, clamped read + select
@@ -54,10 +66,7 @@ msda_fwd_vec(const BT *__restrict__ value, const int64_t *__restrict__ shapes,
     constexpr int STRIDE = 2 * KC + 1;            // uint4 units; +1 breaks the bank alignment
     __shared__ uint4 lds[QPB * STRIDE];
     __shared__ LevelLds levels;
-    // taps of the chunk that weigh something for at least one query of a wave: bit kk of the wave's word
-    // (set while staging; the gather walks the set bits, so a tap nobody needs is never issued and the walk
-    // has a counted trip -- the shape the compiler's wait-count pass pipelines cleanly)
-    constexpr bool kPipe = BUF && KC <= 64;
+    constexpr bool kPipe = BUF && KC <= 64;                // live words + the pipelined walk (msda_gather.h)
     constexpr int QPW = 64 / LPI > 0 ? 64 / LPI : 1;       // queries per wave
     __shared__ unsigned long long live[kThreads / 64];
 
@@ -91,146 +100,70 @@ msda_fwd_vec(const BT *__restrict__ value, const int64_t *__restrict__ shapes,
         // ---- stage: locations + weights -> tap records (coalesced over samples)
         for (int r = tid; r < QPB * kc_pad; r += kThreads) {
             const int rq = r / kc_pad, kk = r - rq * kc_pad;
-            FwdRec rec;
-            rec.row[0] = rec.row[1] = rec.row[2] = rec.row[3] = -1;
-            rec.w[0] = rec.w[1] = rec.w[2] = rec.w[3] = 0.f;
+            float lx = -8.f, ly = -8.f, a = 0.f;                  // padding: outside every map, weight 0
+            int Hl = 1, Wl = 1, lstart = 0;
             const int sq = bc.q0 + rq;
             if (kk < kc && sq < d.Nq) {
                 const int k = k0 + kk;
                 const int l = k / d.P;
                 const int64_t s = (((int64_t)bc.b * d.Nq + sq) * d.H + bc.h) * d.K + k;
-                float lx, ly;
                 load_xy(loc, s, pair_ok, lx, ly);
-                const float a = to_f32(attn[s]);
-                int Hl, Wl, lstart;
+                a = to_f32(attn[s]);
                 levels.get(shapes, start, l, Hl, Wl, lstart);
-                const Tap<float> t = locate<float>(lx, ly, Hl, Wl, lstart);
-                const float gy = 1.f - t.fy, gx = 1.f - t.fx;
-                // a zero attention weight (an image the token cannot see: the masked softmax gives
-                // exactly 0, mmfs.py:203-231) reads no rows at all -- it is marked "outside"
-                if (a != 0.f) {
-                    rec.row[0] = t.row[0]; rec.row[1] = t.row[1]; rec.row[2] = t.row[2]; rec.row[3] = t.row[3];
-                }
-                rec.w[0] = gy * gx * a; rec.w[1] = gy * t.fx * a;
-                rec.w[2] = t.fy * gx * a; rec.w[3] = t.fy * t.fx * a;
             }
+            uint4 rows, ww;
+            if (BUF) tap_record(lx, ly, a, Hl, Wl, lstart, row_bytes, rows, ww);
+            else flat_record(lx, ly, a, Hl, Wl, lstart, d.S, rows, ww);
             uint4 *dst = &lds[rq * STRIDE + 2 * kk];
-            if (!BUF) {
-                // flat addresses have no descriptor to stop a row that a malformed level table puts past S
-#pragma unroll
-                for (int c = 0; c < 4; ++c) rec.row[c] = rec.row[c] < d.S ? rec.row[c] : -1;
-            }
-            if (BUF) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c)      // pixel row -> byte offset in the slab, or "outside"
-                    rec.row[c] = rec.row[c] >= 0 ? (int)((uint32_t)rec.row[c] * row_bytes) : (int)kOobOffset;
-            }
-            dst[0] = make_uint4(rec.row[0], rec.row[1], rec.row[2], rec.row[3]);
-            dst[1] = make_uint4(__float_as_uint(rec.w[0]), __float_as_uint(rec.w[1]),
-                                __float_as_uint(rec.w[2]), __float_as_uint(rec.w[3]));
-            if (kPipe) {
-                const uint32_t any_w = (__float_as_uint(rec.w[0]) | __float_as_uint(rec.w[1]) |
-                                        __float_as_uint(rec.w[2]) | __float_as_uint(rec.w[3])) << 1;   // (-0 is zero too)
-                if (any_w != 0u) atomicOr(&live[rq / QPW], 1ull << kk);
-            }
+            dst[0] = rows;
+            dst[1] = ww;
+            if (kPipe) mark_live<QPW>(live, rq, kk, ww);
         }
         __syncthreads();
         if (kPipe) {
-            // ---- gather, software-pipelined: the 4 row reads of the next live tap are in flight while the
-            // current one is multiplied (4..8 reads in flight per lane)
-            const int wv = tid >> 6;
-            const unsigned long long mraw = live[wv];
-            unsigned long long m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mraw >> 32)) << 32) |
-                                   (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)mraw);
-            if ((tid & 63) == 0) live[wv] = 0ull;                 // (mine; the next chunk's staging sets it after the barrier)
+            gather_live<V>(take_live(live, tid), &lds[qi * STRIDE], rsrc, lane_off, acc);
+        } else if (q_ok) {
             const uint4 *recs = &lds[qi * STRIDE];
-            uint4 rawA[4], rawB[4], wA, wB;
-            auto issue = [&](uint4 (&raw)[4], uint4 &ww) {
-                const int kk = __builtin_ctzll(m);
-                m &= m - 1ull;
-                const uint4 rr = recs[2 * kk];
-                ww = recs[2 * kk + 1];
-                raw[0] = buffer_load16(rsrc, rr.x + lane_off);
-                raw[1] = buffer_load16(rsrc, rr.y + lane_off);
-                raw[2] = buffer_load16(rsrc, rr.z + lane_off);
-                raw[3] = buffer_load16(rsrc, rr.w + lane_off);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            auto consume = [&](const uint4 (&raw)[4], const uint4 &ww) {
-                const float w4[4] = {__uint_as_float(ww.x), __uint_as_float(ww.y), __uint_as_float(ww.z), __uint_as_float(ww.w)};
+            if (BUF) {
+                gather_all<V, kUnroll>(recs, kc_pad, rsrc, lane_off, acc);
+            } else {
+                // ---- 64-bit flat addresses: clamped read + select, kUnroll taps in flight per lane
+                for (int kk = 0; kk < kc_pad; kk += kUnroll) {
+                    uint4 raw[kUnroll][4];
+                    float w[kUnroll][4];
+                    bool ok[kUnroll][4];
+                    uint4 rrs[kUnroll];
+                    uint32_t any_w = 0u;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float v[VEC];
-                    V::unpack(raw[c], v);
+                    for (int u = 0; u < kUnroll; ++u) {
+                        rrs[u] = recs[2 * (kk + u)];
+                        const uint4 ww = recs[2 * (kk + u) + 1];
+                        any_w |= (ww.x | ww.y | ww.z | ww.w) << 1;
+                        w[u][0] = __uint_as_float(ww.x); w[u][1] = __uint_as_float(ww.y);
+                        w[u][2] = __uint_as_float(ww.z); w[u][3] = __uint_as_float(ww.w);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(any_w != 0u) == 0ull) continue;      // (as gather_all)
 #pragma unroll
-                    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w4[c], v[i], acc[i]);
-                }
+                    for (int u = 0; u < kUnroll; ++u) {
+                        const uint4 rr = rrs[u];
+                        const int rows[4] = {(int)rr.x, (int)rr.y, (int)rr.z, (int)rr.w};
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) asm volatile("" : "+v"(acc[i]));     // the sums are due HERE, not after the next reads
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            const int n_live = __builtin_popcountll(m);
-            if (n_live & 1) { issue(rawA, wA); consume(rawA, wA); }
-            if (n_live >= 2) {
-                issue(rawA, wA);
-                for (int i = 2; i < n_live - 1; i += 2) {
-                    issue(rawB, wB);
-                    consume(rawA, wA);
-                    issue(rawA, wA);
-                    consume(rawB, wB);
-                }
-                issue(rawB, wB);
-                consume(rawA, wA);
-                consume(rawB, wB);
-            }
-        } else
-        // ---- gather: kUnroll taps (4*kUnroll row reads) in flight per lane
-        if (q_ok) {
-            const uint4 *recs = &lds[qi * STRIDE];
-            for (int kk = 0; kk < kc_pad; kk += kUnroll) {
-                uint4 raw[kUnroll][4];
-                float w[kUnroll][4];
-                bool ok[kUnroll][4];
-                uint4 rrs[kUnroll];
-                uint32_t any_w = 0u;
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    rrs[u] = recs[2 * (kk + u)];
-                    const uint4 ww = recs[2 * (kk + u) + 1];
-                    any_w |= (ww.x | ww.y | ww.z | ww.w) << 1;          // (sign bit aside: -0 is zero too)
-                    w[u][0] = __uint_as_float(ww.x); w[u][1] = __uint_as_float(ww.y);
-                    w[u][2] = __uint_as_float(ww.z); w[u][3] = __uint_as_float(ww.w);
-                }
-                // every tap of every query of this wave weighs zero (consecutive tokens share what
-                // they can see, so whole waves are blind to an image): nothing to read, nothing to add.
-                // An "outside" row costs no data but its load still costs the address path its cycles.
-                if (__builtin_amdgcn_ballot_w64(any_w != 0u) == 0ull) continue;
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const uint4 rr = rrs[u];
-                    const int rows[4] = {(int)rr.x, (int)rr.y, (int)rr.z, (int)rr.w};
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (BUF) {
-                            ok[u][c] = true;
-                            raw[u][c] = buffer_load16(rsrc, (uint32_t)rows[c] + lane_off);
-                        } else {
+                        for (int c = 0; c < 4; ++c) {
                             ok[u][c] = rows[c] >= 0;
                             const int64_t off = (int64_t)max(rows[c], 0) * HD;
                             raw[u][c] = *reinterpret_cast<const uint4 *>(vbase + off);
                         }
                     }
-                }
 #pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
+                    for (int u = 0; u < kUnroll; ++u) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float v[VEC];
-                        V::unpack(raw[u][c], v);
-                        const float wc = w[u][c];
+                        for (int c = 0; c < 4; ++c) {
+                            float v[VEC];
+                            V::unpack(raw[u][c], v);
+                            const float wc = w[u][c];
 #pragma unroll
-                        for (int i = 0; i < VEC; ++i)
-                            acc[i] = fmaf(wc, (BUF || ok[u][c]) ? v[i] : 0.f, acc[i]);
+                            for (int i = 0; i < VEC; ++i) acc[i] = fmaf(wc, ok[u][c] ? v[i] : 0.f, acc[i]);
+                        }
                     }
                 }
             }

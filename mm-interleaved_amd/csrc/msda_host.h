@@ -1,0 +1,39 @@
+// msda_host.h -- the small host-side checks and dispatchers that every extern "C" entry shares.
+#pragma once
+#include "../../include/mmfs_msda.h"
+#include "msda_device.h"
+#include <stdint.h>
+
+namespace mmfs {
+
+// bytes of an element of ``dtype`` (enum mmfs_dtype), 0 for a type the caller does not serve (fp64: only the op does)
+inline int elem_size(int dtype, bool f64 = false)
+{
+    switch (dtype) {
+        case MMFS_F32: return 4;
+        case MMFS_F16: case MMFS_BF16: return 2;
+        case MMFS_F64: return f64 ? 8 : 0;
+        default: return 0;
+    }
+}
+
+// rows ``ld`` elements apart (0 = packed, ``cols``), vector accesses of ``vec`` elements of ``es`` bytes: dimensions and
+// alignment (load_row / store_row: accesses of at most 16 bytes)
+inline int heads_rows(int64_t &ld, int64_t cols, const void *p, int64_t vec, int64_t es)
+{
+    if (ld == 0) ld = cols;
+    if (ld < cols || ld > 0x7fffffffLL) return MMFS_E_DIMS;
+    const int64_t a = vec * es < 16 ? vec * es : 16;
+    if ((ld * es) % a || (uintptr_t)p % (uintptr_t)a) return MMFS_E_ALIGN;
+    return MMFS_OK;
+}
+
+// f(T()) for the storage type of a dtype that elem_size serves without fp64
+template <typename F> int by_type(int dtype, F &&f)
+{
+    if (dtype == MMFS_F32) return f(float());
+    if (dtype == MMFS_F16) return f(half_t());
+    return f(bf16_t());
+}
+
+}  // namespace mmfs

@@ -234,6 +234,62 @@ def test_sampler_after_the_plan_on_the_plans_own_numbers(dtype, P, monkeypatch):
     print(f"PLAN-MMFS-BOUNDS {name(dtype)} P={P} sampler on the plan's numbers: out {rep['out']:.3f}")
 
 
+SAMPLER_WALKS = [
+    # dtype, D: lanes per query = D * element size / 16; a chunk holds max(2 * lanes, P) samples per query
+    (torch.float32, 16, "4 lanes: the 8 samples are one chunk of the pipelined walk"),
+    (torch.bfloat16, 32, "4 lanes, 16-bit rows"),
+    (torch.float32, 256, "64 lanes: the walk without live words, a wave per query"),
+    (torch.bfloat16, 8, "1 lane: chunks of 4 samples, two per query"),
+]
+
+
+@pytest.mark.parametrize("live", [0, 1, 2, 3, 4, 5, 8, "image"])
+@pytest.mark.parametrize("dtype,D,what", SAMPLER_WALKS, ids=[f"{name(w[0])}-D{w[1]}" for w in SAMPLER_WALKS])
+def test_fused_sampler_walks_at_their_smallest(dtype, D, what, live, monkeypatch):
+    """mmfs_sample_fwd's walks over a chunk's tap records where each branch is alone, equal bit for bit to the plan kernel
+    followed by the op's row gather: three queries (a ragged tile) of one head with 8 samples each (levels 3 x 5 and
+    2 x 2, P = 4), of which the first ``live`` keep their logit and the others get -1e4 -- a softmax weight of exactly 0
+    in every storage type, so their taps are not walked: no live tap, the odd prologue alone, the pair without the loop,
+    one loop trip, every tap.  "image": two images of one level each, the first one invisible (relpos 0).  The middle
+    query of sample 0 weighs nothing at all: with 64 lanes per query it is a wave that skips every pair."""
+    import MultiScaleDeformableAttention as MSDA
+    from mmfs_amd.functions.mmfs_plan_func import mmfs_sample_forward, sample_forward_groups
+    helpers.poison_allocations(monkeypatch)
+    monkeypatch.setenv("MMFS_SAMPLE_DECODE", "0")            # (3 queries are decode-sized: this is about mmfs_sample_fwd)
+    n, L = (2, 1) if live == "image" else (1, 2)
+    Lq, H, P, N = 3, 1, 4, N_PLAN
+    assert sample_forward_groups(dtype, Lq, D, n * L, P) == 1
+    c = plan_inputs(dtype, n, L, Lq, Lq, N, H, P, "", seed=77)
+    c["shapes"] = torch.tensor([(3, 5), (2, 2)], device=DEV)
+    att = c["both"][..., c["n_off"]:]                        # [N, Lq, L * P]: the logits in sample order for one image
+    if live == "image":
+        c["relpos"][:, :, 0] = 0
+        dead = torch.arange(8, device=DEV) < 4
+    else:
+        dead = torch.arange(8, device=DEV) >= live
+        att[..., dead] = -1e4
+        att[0, 1] = -1e4
+    dims = (N, Lq, H, L, P, n, M_PLAN, Lq, N)
+    loc, attn, sink = plan_forward(dtype, c, dims, stacked=False)
+    assert not bool(attn.reshape(N, Lq, 8)[..., dead].any()) and bool(attn.reshape(N, Lq, 8)[1][..., ~dead].all())
+    sh, st = helpers.level_tables(c["shapes"].tolist(), DEV)
+    g = torch.Generator(device=DEV).manual_seed(5)
+    value = torch.rand(N, 19, H, D, device=DEV, generator=g).to(dtype)
+    token = torch.randn(H, D, device=DEV, generator=g).to(dtype)
+    old, MSDA._fwd_algo = MSDA._fwd_algo, "gather"
+    try:
+        op = MSDA.ms_deform_attn_forward(value, sh, st, loc, attn, 64)
+    finally:
+        MSDA._fwd_algo = old
+    for tok in (None, token):
+        fused = mmfs_sample_forward(value, sh, st, *c["packed"], c["relpos"], c["ref"], c["ratios"], H, L, P, token=tok)
+        assert fused is not None, what
+        want = op if tok is None else op + (tok.reshape(1, 1, H * D) * sink.to(dtype).repeat_interleave(D, -1)).to(dtype)
+        assert torch.equal(fused[0], want) and torch.equal(fused[1], sink), what
+    if live == 0:
+        assert not bool(op.any())
+
+
 # --------------------------------------------------------------------------------------------- the RMS norm
 NORM_ROWS = (1, 3, 5, 74, 2049, 24581)
 

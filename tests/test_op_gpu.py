@@ -1138,6 +1138,33 @@ def test_forward_formulations_take_locations_that_start_on_an_odd_element(algo):
     assert max_abs(a.double().cpu().numpy(), want) <= TOL[torch.bfloat16]
 
 
+WALKS = [
+    # dtype, D: lanes per query = D * element size / 16; a chunk holds 2 * lanes samples per query
+    (torch.float32, 16, "4 lanes: the 8 samples are one chunk of the pipelined walk"),
+    (torch.bfloat16, 32, "4 lanes, 16-bit rows"),
+    (torch.float32, 256, "64 lanes: the walk without live words, a wave per query"),
+    (torch.bfloat16, 8, "1 lane: chunks of 2 samples, four per query"),
+]
+
+
+@pytest.mark.parametrize("live", [0, 1, 2, 3, 4, 5, 8])
+@pytest.mark.parametrize("dtype,D,what", WALKS, ids=[f"{str(w[0])[6:]}-D{w[1]}" for w in WALKS])
+def test_row_gather_walks_at_their_smallest(dtype, D, what, live):
+    """The row gather's walks over a chunk's tap records at the shapes where each branch is alone: three queries (a ragged
+    tile) of 8 samples each, of which the first ``live`` weigh something -- the other weights are exactly 0, so their taps
+    are not walked: no live tap at all, the odd prologue alone (1), the pair without the loop (2, 3), one loop trip (4, 5),
+    every tap (8).  The middle query weighs nothing at all: with 64 lanes per query it is a wave that skips every pair.
+    Against the oracle under the per-element bound."""
+    x = make_inputs(1, 1, D, 3, 4, [(3, 5), (2, 2)], seed=41, loc_range=(0.1, 0.9), dtype=dtype)
+    keep = torch.zeros(1, 3, 1, 8, dtype=torch.float64)
+    keep[..., :live] = 1.0
+    keep[:, 1] = 0.0
+    x["attn"] = x["attn"] * keep.reshape(1, 3, 1, 2, 4)
+    got = run_fwd(x, dtype, "gather")
+    assert_within_bounds([got, None, None, None], x, dtype, f"{what}, {live} live", outputs=("out",))
+    assert not got[0, 1].any() and (live == 0) == (not got.any())
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype,code", [(torch.float32, 0), (torch.float16, 1), (torch.bfloat16, 2)])
 def test_cast_from_f32_entry_point(dtype, code):

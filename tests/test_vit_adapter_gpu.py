@@ -186,6 +186,37 @@ def test_fused_sampler_against_the_oracle_on_the_plans_own_numbers(dtype, D, mon
     assert deform_sample_forward(c["value"], c["shapes"], c["start"], c["both"], c["ref"], 3, 1, 4) is None
 
 
+SAMPLER_WALKS = [(torch.float32, 16, "4 lanes per query: the 8 samples are one chunk"), (torch.bfloat16, 32, "4 lanes, 16-bit rows"),
+                 (torch.bfloat16, 16, "2 lanes: chunks of 4 samples, two per query")]
+
+
+@pytest.mark.parametrize("live,R", [(1, 2), (2, 2), (3, 4), (4, 2), (5, 4), (8, 2)])
+@pytest.mark.parametrize("dtype,D,what", SAMPLER_WALKS, ids=[f"{str(w[0])[6:]}-D{w[1]}" for w in SAMPLER_WALKS])
+def test_fused_sampler_walk_at_its_smallest(dtype, D, what, live, R, monkeypatch):
+    """deform_sample_fwd's walk over a chunk's live tap records where each branch is alone, equal bit for bit to the plan
+    kernel followed by the op's row gather: three queries (a ragged tile; the workgroup's other waves hold no query at
+    all and walk nothing) of one head with 8 samples each (levels 3 x 5 and 2 x 2, P = 4), of which the first ``live``
+    keep their logit and the others get -1e4 -- a softmax weight of exactly 0 in every storage type, so their taps are
+    not walked: the odd prologue alone, the pair without the loop, one loop trip, every tap."""
+    import MultiScaleDeformableAttention as MSDA
+    from mmfs_amd.functions import DeformPlanFunction, deform_sample_forward
+    helpers.poison_allocations(monkeypatch)
+    N, Lq, H, L, P = 2, 3, 1, 2, 4
+    c = sampler_case(dtype, [(3, 5), (2, 2)], P, R, D, N, Lq, H, seed=900 + live)
+    c["both"][..., c["n_off"] + live:] = -1e4
+    loc, attn = DeformPlanFunction.apply(c["both"], c["ref"], c["shapes"], H, L, P)
+    w = attn.reshape(N, Lq, L * P)
+    assert not bool(w[..., live:].any()) and bool(w[..., :live].all())
+    old, MSDA._fwd_algo = MSDA._fwd_algo, "gather"
+    try:
+        op = MSDA.ms_deform_attn_forward(c["value"], c["shapes"], c["start"], loc, attn, 64)
+    finally:
+        MSDA._fwd_algo = old
+    out = deform_sample_forward(c["value"], c["shapes"], c["start"], c["both"], c["ref"], H, L, P)
+    assert out is not None, what
+    assert torch.equal(out, op) and bool(op.any()), what
+
+
 # ------------------------------------------------------------------ the module on the committed encoder goldens
 def enc_module(name, dtype):
     from mmfs_amd.modules import MSDeformAttn
