@@ -381,8 +381,8 @@ int mmfs_msda_backward_hybrid(int dtype,
  * records' grad_out rows -- no value row is gathered per sample (the gather kernels: 4 rows per sample through the
  * vector-memory path).  Same results within the storage type's rounding (same products, fp32 sums in another order).
  * Applies to MMFS_F16 / MMFS_BF16, D in {32, 64, 128}, P a power of two with Nq * P <= 65536, a level table the HOST has
- * verified (MMFS_BWD_CANONICAL_LEVELS in ``flags``) and shapes whose sort keeps its samples in registers (Nq <= 4096 per
- * vector group); otherwise *_workspace_bytes returns 0 and the call MMFS_E_UNSUPPORTED: use mmfs_msda_backward[_hybrid].
+ * verified (MMFS_BWD_CANONICAL_LEVELS in ``flags``), a value slab S * H * D * 2 of less than 2 GiB and shapes whose sort
+ * keeps its samples in registers (Nq <= 4096 per vector group); otherwise *_workspace_bytes returns 0 and the call MMFS_E_UNSUPPORTED: use mmfs_msda_backward[_hybrid].
  * MMFS_BWD_LAZY_ZERO_ATTN as there.  ``stages``: OR of the bits, all of them = the whole pass, in this order (each stage
  * needs the ones before it on the same workspace, and ``loc`` / ``attn`` unchanged until the sort has run).
  */

@@ -444,23 +444,34 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     code = _DTYPE_CODE[value.dtype]
     with _on_device(value.device):
         stream = _stream(value.device)
-        if value_repeat is None:
-            status = _launch(
-                "msda_fwd", value.device, _lib.mmfs_msda_forward_flags, code, value.data_ptr(), spatial_shapes.data_ptr(),
+
+        def launch(name, flags):
+            if value_repeat is None:
+                return _launch(
+                    name, value.device, _lib.mmfs_msda_forward_flags, code, value.data_ptr(), spatial_shapes.data_ptr(),
+                    level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                    out.data_ptr(), B, S, H, D, L, Nq, P, flags, stream)
+            return _launch(
+                name, value.device, _lib.mmfs_msda_forward_shared, code, value.data_ptr(), spatial_shapes.data_ptr(),
                 level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                out.data_ptr(), B, S, H, D, L, Nq, P, _FWD_FLAGS[_fwd_algo], stream)
+                out.data_ptr(), B, Bv, _VALUE_REPEAT[value_repeat], S, H, D, L, Nq, P, flags, stream)
+        if _fwd_algo in ("lds", "slices", "waves") and S * H * D * value.element_size() > _MAX_SLAB_BYTES:
+            # none of the kernels that can be asked for by name takes a (b) slab its 32-bit row offsets cannot span
+            # (csrc/msda_device.h, kMaxSlabBytes): the row gather's flat-address kernel serves the call, as it does under
+            # "auto" and as the backward does for its named LDS-levels kernel -- decided here, on the size alone, whatever
+            # else the named kernel would have refused.  Under the limit a named kernel's refusal raises, as before.
+            status = launch("msda_fwd_gather", _FWD_FLAGS["gather"])
         else:
-            status = _launch(
-                "msda_fwd", value.device, _lib.mmfs_msda_forward_shared, code, value.data_ptr(), spatial_shapes.data_ptr(),
-                level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                out.data_ptr(), B, Bv, _VALUE_REPEAT[value_repeat], S, H, D, L, Nq, P, _FWD_FLAGS[_fwd_algo], stream)
+            status = launch("msda_fwd", _FWD_FLAGS[_fwd_algo])
     _check(status, "ms_deform_attn_forward")
     return out
 
 
 # tests / measurements: which formulation of the forward runs (include/mmfs_msda.h, mmfs_msda_forward_flags):
-# "auto" | "gather" (csrc/msda_fwd.hip) | "lds" (csrc/msda_fwd_mma.hip; unsupported shapes raise)
+# "auto" | "gather" (csrc/msda_fwd.hip) | "lds" (csrc/msda_fwd_mma.hip; unsupported shapes raise -- but a value slab of
+# 2 GiB or more, which none of the named kernels takes, goes to the row gather: logged as "msda_fwd_gather")
 _fwd_algo = "auto"
+_MAX_SLAB_BYTES = 0x7fffffff      # kMaxSlabBytes of csrc/msda_device.h: what a buffer descriptor's 32-bit byte offsets span
 _FWD_FLAGS = {"auto": 0, "gather": 1, "lds": 2, "slices": 4, "waves": 8}        # "slices": csrc/msda_fwd_q8.hip; "waves": msda_fwd_wq.hip
 
 
@@ -650,7 +661,12 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     dt = value.dtype
     code = _DTYPE_CODE[dt]
     dims = (B, S, H, D, L, Nq, P)
-    flags = (_BWD_LAZY_ZERO_ATTN if lazy_zero_attn else 0) | _TAPS_FLAGS[_taps_algo]
+    taps = _taps_algo
+    if taps == "lds" and S * H * D * value.element_size() > _MAX_SLAB_BYTES:
+        # (as the forward: the LDS-levels kernel named for a value slab its 32-bit row offsets cannot span -- a matter of
+        # size, so the call goes to the row gather's flat-address kernel instead of raising)
+        taps = "gather"
+    flags = (_BWD_LAZY_ZERO_ATTN if lazy_zero_attn else 0) | _TAPS_FLAGS[taps]
     info = None
     if _bwd_algo == "atomic":
         flags |= _BWD_FORCE_ATOMIC
@@ -681,7 +697,12 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
                 if len(_ws_cache) > 4096:
                     _ws_cache.clear()
                 srt_bytes = _ws_cache[skey] = _lib.mmfs_msda_backward_sorted_workspace_bytes(code, *dims, flags)
-        _require(srt_bytes > 0 or _taps_algo != "sorted", "taps algo 'sorted': mmfs_msda_backward_sorted does not apply to these arguments")
+        # ("sorted" by name raises where the route does not apply -- except for a value slab over the limit: the call then
+        # goes on to the routes below, like the other named kernels'.  Decided here, on the size alone, whatever else the
+        # route would have refused -- fp32 storage, an unregistered or non-canonical table, the float-atomic route asked for --:
+        # in those cases srt_bytes is 0 without the library having been asked.)
+        _require(srt_bytes > 0 or _taps_algo != "sorted" or S * H * D * value.element_size() > _MAX_SLAB_BYTES,
+                 "taps algo 'sorted': mmfs_msda_backward_sorted does not apply to these arguments")
         if srt_bytes > 0:
             route_counts["sorted"] += 1
             ws = torch.empty(srt_bytes, dtype=torch.uint8, device=value.device)

@@ -1459,6 +1459,9 @@ bool taps_sorted_supported(int dtype, const Dims &d)
 {
     if (!bwd_value_block_supported(dtype, d) || !tile_reduce_supported(dtype, d)) return false;
     if (d.P <= 0 || (d.P & (d.P - 1)) || (int64_t)d.Nq * d.P > 65536) return false;
+    // a level's value rows are fetched through a buffer descriptor over that level: 31-bit byte offsets and a 32-bit length,
+    // and one level can be the whole (b) slab (a level of 4 GiB would get a length of 0)
+    if ((int64_t)d.S * d.H * d.D * 2 > kMaxSlabBytes) return false;
     if (const char *e = knob_str(K_TAPS_ALGO)) if (e[0] == 'v' || e[0] == 'm' || e[0] == 'g') return false;     // vec / mma / gather
     return sort_keeps_samples(dtype, d, make_params(d));
 }

@@ -252,8 +252,8 @@ __device__ __forceinline__ BatchRec fetch_batch(const uint2 *__restrict__ list, 
 template <typename T, int LPS, bool BUF>
 __device__ __forceinline__ void consume_batch(const BatchRec &mine, int lig, uint2 *__restrict__ slot,
                                               const T *__restrict__ gslice, int64_t HD,
-                                              __amdgpu_buffer_rsrc_t rsrc, uint32_t row_bytes,
-                                              uint32_t lane_off, float (&acc)[Vec16<T>::N])
+                                              __amdgpu_buffer_rsrc_t rsrc, uint32_t lane_off,
+                                              float (&acc)[Vec16<T>::N])
 {
     typedef Vec16<T> V;
     constexpr int U = LPS < kUnroll ? LPS : kUnroll;
@@ -270,8 +270,10 @@ __device__ __forceinline__ void consume_batch(const BatchRec &mine, int lig, uin
             if (BUF) {
                 raw[u] = buffer_load16(rsrc, rec.x + lane_off);
             } else {
+                // flat addresses: the records were fetched with a row pitch of 1, so rec.x is the query index -- below
+                // 2^31, which kOobOffset is not (a byte offset can equal it, and wraps from 4 GiB on)
                 const bool ok = rec.x != kOobOffset;
-                raw[u] = *reinterpret_cast<const uint4 *>(gslice + (int64_t)(ok ? rec.x / row_bytes : 0u) * HD);
+                raw[u] = *reinterpret_cast<const uint4 *>(gslice + (int64_t)(ok ? rec.x : 0u) * HD);
                 if (!ok) raw[u] = make_uint4(0u, 0u, 0u, 0u);   // 0 * Inf must not leak
             }
         }
@@ -373,7 +375,7 @@ msda_bwd_value_reduce(const T *__restrict__ grad_out, T *__restrict__ grad_value
 
     const int64_t HD = (int64_t)d.H * d.D;
     const T *gslice = grad_out + ((int64_t)b * d.Nq * d.H + h) * d.D + lig * VEC;
-    const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
+    const uint32_t row_bytes = BUF ? (uint32_t)(HD * sizeof(T)) : 1u;     // pitch of a record's row offset
     const uint32_t lane_off = (uint32_t)(lig * 16);
     __amdgpu_buffer_rsrc_t rsrc;
     if (BUF) rsrc = make_slab_rsrc(grad_out + ((int64_t)b * d.Nq * d.H + h) * d.D,
@@ -396,7 +398,7 @@ msda_bwd_value_reduce(const T *__restrict__ grad_out, T *__restrict__ grad_value
     for (int j = 0; j < nb; ++j) {
         const BatchRec cur_rec = pre;
         if (j + 1 < nb) pre = fetch_batch(list, (j + 1) * LPS + lig, own, row_bytes);
-        consume_batch<T, LPS, BUF>(cur_rec, lig, slot, gslice, HD, rsrc, row_bytes, lane_off, acc);
+        consume_batch<T, LPS, BUF>(cur_rec, lig, slot, gslice, HD, rsrc, lane_off, acc);
     }
     // ---- phase 2: long runs, pixel by pixel, all groups together
     if (lig == 0) rest[gid] = make_uint2(run.x + (uint32_t)own, (uint32_t)(n - own));
@@ -412,7 +414,7 @@ msda_bwd_value_reduce(const T *__restrict__ grad_out, T *__restrict__ grad_value
         for (int i = 0; i < VEC; ++i) part[i] = 0.f;
         for (int j = gid; j < batches; j += GROUPS) {
             const BatchRec br = fetch_batch(rl, j * LPS + lig, rn, row_bytes);
-            consume_batch<T, LPS, BUF>(br, lig, slot, gslice, HD, rsrc, row_bytes, lane_off, part);
+            consume_batch<T, LPS, BUF>(br, lig, slot, gslice, HD, rsrc, lane_off, part);
         }
 #pragma unroll
         for (int i = 0; i < VEC; ++i) scratch[gid * D + lig * VEC + i] = part[i];

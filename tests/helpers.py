@@ -301,3 +301,61 @@ def assert_within_bounds(got, x, dtype, what="", outputs=OUTPUTS, want=None, gam
     assert not bad, f"{what}: per-element bound broken: " + "; ".join(
         f"{n} {r[0]:.3g} x the bound at {r[1]} (err {r[2]:.3e}, bound {r[3]:.3e})" for n, r in bad.items())
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Problems too large for the oracle as a whole (tests/test_large_slabs*.py): the op's heads are independent -- output
+# head h reads value, loc, attn and grad at head h only -- so restricting the inputs and every output to a set of heads is
+# the same op on a smaller problem, and the oracle and the bound above serve it unchanged.
+# ---------------------------------------------------------------------------------------------------------------------
+def head_subset(x, heads):
+    """-> the input dict of make_inputs reduced to ``heads`` (in that order): value [B, S, n, D], loc [B, Nq, n, L, P, 2],
+    attn [B, Nq, n, L, P], grad [B, Nq, n * D]; the level table and every other key as they are.  Tensors stay on their
+    device and keep their type (the caller rounds / moves them)."""
+    value, loc, attn = (torch.as_tensor(x[k]) for k in ("value", "loc", "attn"))
+    B, S, H, D = value.shape
+    Nq = loc.shape[1]
+    pick = lambda t: t.index_select(2, torch.as_tensor(list(heads), dtype=torch.long, device=t.device))
+    grad = pick(torch.as_tensor(x["grad"]).reshape(B, Nq, H, D))
+    return dict(x, value=pick(value), loc=pick(loc), attn=pick(attn), grad=grad.reshape(B, Nq, -1))
+
+
+def head_subset_outputs(outs, heads, H):
+    """The op's outputs in OUTPUTS order (entries may be None) at ``heads``: out [B, Nq, n * D], grad_value
+    [B, S, n, D], grad_loc [B, Nq, n, L, P, 2], grad_attn [B, Nq, n, L, P]."""
+    pick = lambda t: t.index_select(2, torch.as_tensor(list(heads), dtype=torch.long, device=t.device))
+    res = []
+    for name, t in zip(OUTPUTS, outs):
+        if t is None:
+            res.append(None)
+        elif name == "out":
+            B, Nq = t.shape[:2]
+            res.append(pick(t.reshape(B, Nq, H, -1)).reshape(B, Nq, -1))
+        else:
+            res.append(pick(t))
+    return res
+
+
+def worst_ratio(got, ref, bound, skip=None):
+    """bound_ratios' rule for ONE output on torch tensors, on whatever device they live (an output of 10^8 elements is
+    compared where it was computed): ``ref`` and ``bound`` fp64 of the output's shape, ``skip`` bool (grad_loc's samples
+    near a pixel crossing) or None.  -> (ratio, flat index, error, bound); finiteness that differs, or an error where the
+    bound is 0, gives inf."""
+    ref, bound = ref.double(), bound.double().expand(ref.shape)
+    g = got.double().reshape(ref.shape)
+    if g.numel() == 0:
+        return 0.0, 0, 0.0, 0.0
+    fin = torch.isfinite(ref)
+    odd = torch.isfinite(g) != fin
+    if bool(odd.any()):
+        k = int(odd.reshape(-1).nonzero()[0])
+        return float("inf"), k, float(g.reshape(-1)[k]), float(ref.reshape(-1)[k])
+    use = fin & torch.isfinite(bound)
+    if skip is not None:
+        use &= ~skip
+    zero, inf = torch.zeros((), dtype=torch.float64, device=g.device), torch.full((), float("inf"), dtype=torch.float64, device=g.device)
+    err = torch.where(use, (g - ref).abs(), zero)
+    pos = bound > 0
+    ratio = torch.where(pos, err / torch.where(pos, bound, zero + 1.0), torch.where(err > 0, inf, zero))
+    k = int(ratio.reshape(-1).argmax())
+    return float(ratio.reshape(-1)[k]), k, float(err.reshape(-1)[k]), float(bound.reshape(-1)[k])
