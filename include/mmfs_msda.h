@@ -36,7 +36,10 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_pyramid_head_supported / _forward / _backward: the ViT-Adapter's output pyramid from the
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_sequence_supported / _index / _embed_forward / _embed_backward / _context_forward /
+                                   *     _context_backward_workspace_bytes / _context_backward: the interleaved sequence (embeddings and the image
+                                   *     decoder's context) built on the device, see "The interleaved sequence" below
+                                   * 14 (additive): + mmfs_pyramid_head_supported / _forward / _backward: the ViT-Adapter's output pyramid from the
                                    *     tokens, packed for the feature bank, see "The adapter's output pyramid" below
                                    * 14 (additive): + mmfs_dwconv_tokens_supported / _forward / _backward_workspace_bytes / _backward: the depthwise
                                    *     convolution of the ViT-Adapter's ConvFFN in the token layout, see "ConvFFN's depthwise convolution" below
@@ -681,6 +684,64 @@ int mmfs_pyramid_head_forward(int dtype, const void *c, const void *x1, const vo
 int mmfs_pyramid_head_backward(int dtype, const void *grad_out, void *grad_up, void *grad_c1, void *grad_x1, void *grad_x2,
                                void *grad_x3, void *grad_x4, int64_t B, int64_t H, int64_t W, int64_t C, int levels,
                                int c1_layout, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The interleaved sequence (csrc/mmfs_sequence.hip; additive at ABI 14).  Replaces step 3 of _prepare_mm_embeds
+ * (mm_interleaved/models/mm_interleaved.py:144-171: two nonzero(), a cast, a scatter, a scatter_add) and
+ * _prepare_context_features_for_image_decoder (:254-304: two nonzero(), a Python loop over the images that slices with device
+ * scalars, a projection of every padded row, a sin-cos table built on the host per call).  No entry reads anything back, allocates
+ * or synchronises: all of them can be captured into a graph.  T is the storage type ``dtype`` (MMFS_F32 / MMFS_F16 / MMFS_BF16),
+ * C * sizeof(T) a multiple of 16 and C > 0 (mmfs_sequence_supported; otherwise MMFS_E_UNSUPPORTED and the caller keeps the
+ * framework's statements).  Arithmetic is fp32 with ONE rounding; copies move bits.
+ *
+ * mmfs_sequence_index: text_ids [B, L] int64 -> int32 tables, one launch (B * L, n_vis, n_images <= 2^22 each):
+ *   img_rank [B L]       the row-major rank of an image token; -1 for another token and for a rank >= n_vis
+ *   img_pos  [n_vis]     the flat position of the k-th image token; -1 where there is none
+ *   soi_row, soi_col [n_images]   row and column of the k-th <soi>, row-major; -1 past the last one
+ *   row_first [B + 1]    the images of row b are row_first[b] .. row_first[b + 1] - 1 (entries at most n_images)
+ *   counts   [2]         image tokens and <soi> tokens found (not clamped: the caller's optional validation)
+ * mmfs_sequence_embed_forward: out [rows, C] of T, rows = B L:  out[r] = img_rank[r] >= 0 ? vis[img_rank[r]] : T(text[r]);
+ *   ``text`` [rows, C] is stored as ``text_dtype``: ``dtype`` or MMFS_F32.  A row with text_ids[r] == soi_token_id then becomes
+ *   round_T(float(out[r]) + float(soi_token)).  vis [n_vis, C], soi_token [C] of T; the tables must come from an index call with
+ *   this n_vis.
+ * mmfs_sequence_embed_backward: from grad [rows, C] of T: grad_text[r] = img_rank[r] >= 0 ? 0 : grad[r] (``text_dtype``);
+ *   grad_vis[k] = img_pos[k] >= 0 ? grad[img_pos[k]] : 0;  grad_soi = the sum of grad over the first min(counts[1], n_images) <soi>
+ *   rows in ascending order.  Every element of an output is written; a NULL output is a gradient nobody needs.
+ * mmfs_sequence_context_forward: image i < n_images has the window row_i = soi_row[i], col_i = start_idx[i] (or soi_col[i] when
+ *   start_idx is NULL), bos_i = max(bos_idx[i], 0) (or 0), len_i = col_i - bos_i + 1 -- 0 when row_i < 0 or col_i is outside
+ *   [0, L) -- clamped to [0, max_len]:
+ *     out [n_images, max_len, C]:  out[i, j] = round_T(float(src[row_i, col_i - j]) + float(pos[j]))  for j < len_i,
+ *                                             round_T(float(pad_row) + float(pos[j]))                elsewhere
+ *     mask [n_images, max_len] int64: j < len_i
+ *   src [B, L, C], pad_row [C] or NULL (= 0), pos [seq_len, C] or NULL (the value is then copied, not added), all of T.
+ * mmfs_sequence_context_backward: from grad_out [n_images, max_len, C]: grad_src [B, L, C], token (b, t) the sum over the images
+ *   of row b (row_first) whose window covers it, ascending; grad_pad [C] the sum of the padded rows, per image in ascending j into
+ *   ``workspace`` (mmfs_sequence_context_backward_workspace_bytes, 16-byte aligned, every element written) and then over the
+ *   images in ascending order.  Either output may be NULL.  No atomics, nothing to clear, bit-reproducible.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code, MMFS_F64); MMFS_E_DIMS for a negative size, max_len < 1,
+ * max_len > seq_len or a size beyond 2^22; MMFS_E_UNSUPPORTED for what mmfs_sequence_supported refuses or a ``text_dtype`` that
+ * is neither ``dtype`` nor MMFS_F32; MMFS_E_NULLPTR for a NULL required pointer of a non-empty problem; MMFS_E_ALIGN for a
+ * tensor of T that is not 16-byte aligned (tables: their element size). */
+int mmfs_sequence_supported(int dtype, int64_t C);
+int mmfs_sequence_index(const int64_t *text_ids, int64_t B, int64_t L, int64_t image_token_id, int64_t soi_token_id,
+                        int64_t n_vis, int64_t n_images, int32_t *img_rank, int32_t *img_pos, int32_t *soi_row,
+                        int32_t *soi_col, int32_t *row_first, int32_t *counts, void *stream);
+int mmfs_sequence_embed_forward(int dtype, int text_dtype, const void *text, const void *vis, const void *soi_token,
+                                const int64_t *text_ids, int64_t soi_token_id, const int32_t *img_rank, void *out,
+                                int64_t rows, int64_t C, int64_t n_vis, void *stream);
+int mmfs_sequence_embed_backward(int dtype, int text_dtype, const void *grad, const int32_t *img_rank, const int32_t *img_pos,
+                                 const int32_t *soi_row, const int32_t *soi_col, const int32_t *counts, void *grad_text,
+                                 void *grad_vis, void *grad_soi, int64_t rows, int64_t L, int64_t C, int64_t n_vis,
+                                 int64_t n_images, void *stream);
+int mmfs_sequence_context_forward(int dtype, const void *src, const void *pad_row, const void *pos, const int32_t *soi_row,
+                                  const int32_t *soi_col, const int64_t *start_idx, const int64_t *bos_idx, void *out,
+                                  int64_t *mask, int64_t B, int64_t L, int64_t C, int64_t n_images, int64_t max_len,
+                                  int64_t seq_len, void *stream);
+int64_t mmfs_sequence_context_backward_workspace_bytes(int dtype, int64_t C, int64_t n_images);
+int mmfs_sequence_context_backward(int dtype, const void *grad_out, const int32_t *soi_row, const int32_t *soi_col,
+                                   const int32_t *row_first, const int64_t *start_idx, const int64_t *bos_idx, void *grad_src,
+                                   void *grad_pad, void *workspace, int64_t B, int64_t L, int64_t C, int64_t n_images,
+                                   int64_t max_len, int64_t seq_len, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

@@ -8,8 +8,12 @@ and the callers either side of the op:
     mmfs_amd.blocks      LlamaMMFSAttention, MMFSBlock, MMFSNet; the image encoder's ViT-Adapter blocks
                          (Injector, Extractor, InteractionBlock, InteractionBlockWithCls, deform_inputs)
     mmfs_amd.bank        feature-bank builders + the RCCL all-gather of image features
+    mmfs_amd.sequence    the interleaved sequence: embeddings with the visual rows and <soi> in place, the image decoder's
+                         per-image context, the special-token tables both read
 """
 from .functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch  # noqa: F401
 from .levels import invalidate_caches  # noqa: F401
+from .sequence import (SequenceTables, assemble_mm_embeds, prepare_context_features_for_image_decoder,  # noqa: F401
+                       sequence_tables, sincos_1d_table)
 
 __version__ = "0.1.0"

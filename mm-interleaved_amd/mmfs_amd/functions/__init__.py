@@ -6,3 +6,4 @@ from .norm_func import RMSNormFunction, rmsnorm_supported  # noqa: F401,E402
 from .deform_plan_func import DeformPlanFunction, deform_plan_supported, deform_sample_forward  # noqa: F401,E402
 from .dwconv_func import DWConvTokensFunction, dwconv_tokens_supported  # noqa: F401,E402
 from .pyramid_func import PyramidHeadFunction, pyramid_head_supported  # noqa: F401,E402
+from .sequence_func import ContextGatherFunction, SequenceEmbedFunction, sequence_supported  # noqa: F401,E402
