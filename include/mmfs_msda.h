@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_sequence_supported / _index / _embed_forward / _embed_backward / _context_forward /
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_text_loss_supported / _forward / _backward, MMFS_TEXT_LOSS_*: the text loss (cross-entropy of
+                                   *     the text decoder's 16-bit logits and its gradient) on the device, see "The text loss" below
+                                   * 14 (additive): + mmfs_sequence_supported / _index / _embed_forward / _embed_backward / _context_forward /
                                    *     _context_backward_workspace_bytes / _context_backward: the interleaved sequence (embeddings and the image
                                    *     decoder's context) built on the device, see "The interleaved sequence" below
                                    * 14 (additive): + mmfs_pyramid_head_supported / _forward / _backward: the ViT-Adapter's output pyramid from the
@@ -742,6 +744,41 @@ int mmfs_sequence_context_backward(int dtype, const void *grad_out, const int32_
                                    const int32_t *row_first, const int64_t *start_idx, const int64_t *bos_idx, void *grad_src,
                                    void *grad_pad, void *workspace, int64_t B, int64_t L, int64_t C, int64_t n_images,
                                    int64_t max_len, int64_t seq_len, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The text loss (csrc/mmfs_text_loss.hip; additive at ABI 14).  Replaces the last statement of the training step
+ * (mm_interleaved/models/mm_interleaved.py:449-476: a cast of the logits to fp32, "b n c -> b c n", a sliced copy and
+ * F.cross_entropy, and the same passes backwards) by one read of the logits forward and one read and one write backward.  No
+ * entry reads anything back, allocates or synchronises: all of them can be captured into a graph.  T is the storage type
+ * ``dtype`` (MMFS_F32 / MMFS_F16 / MMFS_BF16) of logits [B, L, V] and grad [B, L, V]; 1 <= V <= 2^24, any V: a row need not be a
+ * whole number of 16-byte vectors (mmfs_text_loss_supported; otherwise MMFS_E_UNSUPPORTED and the caller keeps the framework's
+ * statement).  Arithmetic is fp32 from the stored logits.
+ *
+ * Row (b, first + j), j < n, is scored against labels [B, n] int64; first + n <= L.  A label equal to ``ignore_index`` is
+ * ignored; a label outside [0, V) that is not ``ignore_index`` is OUT OF RANGE: its row counts as ignored, nothing is read
+ * through it, and it is counted.  ``reduction``: MMFS_TEXT_LOSS_NONE / _SUM / _MEAN.
+ * mmfs_text_loss_forward: two launches.
+ *   lse  [B, n] fp32     log sum_i exp(logits[b, first + j, i]) of a valid row, 0 of any other row (which is not read)
+ *   loss [B, n] fp32     lse - logits[b, first + j, label] of a valid row, 0 of any other row
+ *   out  [1]    fp32     the sum of loss in a fixed order (_SUM), divided by the number of valid rows (_MEAN: NaN when there is
+ *                        none); not written and may be NULL for _NONE
+ *   counts [2]  int32    valid rows, out-of-range rows
+ * mmfs_text_loss_backward: one launch; EVERY element of grad is written.  A valid row:
+ *     grad[b, first + j, i] = round_T((exp(logits[b, first + j, i] - lse[b, j]) - (i == label)) * g)
+ *   with g = upstream[b, j] (_NONE), upstream[0] (_SUM) or upstream[0] / counts[0] (_MEAN), all fp32 on the device; every other
+ *   row, the rows outside [first, first + n) included, is zeros.  grad leaves with the non-temporal hint.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code, MMFS_F64); MMFS_E_DIMS for a negative size, first + n > L,
+ * B * L > 2^22 or V > 2^24; MMFS_E_UNSUPPORTED for V = 0 with rows to score or an unknown ``reduction``; MMFS_E_NULLPTR for
+ * a NULL required pointer of a non-empty problem (``counts`` always; ``out`` unless _NONE); MMFS_E_ALIGN for logits or grad that
+ * are not 16-byte aligned (the other tensors: their element size). */
+enum mmfs_text_loss_reduction { MMFS_TEXT_LOSS_NONE = 0, MMFS_TEXT_LOSS_SUM = 1, MMFS_TEXT_LOSS_MEAN = 2 };
+int mmfs_text_loss_supported(int dtype, int64_t V);
+int mmfs_text_loss_forward(int dtype, const void *logits, const int64_t *labels, float *loss, float *lse, float *out,
+                           int32_t *counts, int64_t B, int64_t L, int64_t V, int64_t first, int64_t n, int64_t ignore_index,
+                           int reduction, void *stream);
+int mmfs_text_loss_backward(int dtype, const void *logits, const int64_t *labels, const float *lse, const float *upstream,
+                            const int32_t *counts, void *grad, int64_t B, int64_t L, int64_t V, int64_t first, int64_t n,
+                            int64_t ignore_index, int reduction, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

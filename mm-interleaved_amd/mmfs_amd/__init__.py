@@ -10,10 +10,14 @@ and the callers either side of the op:
     mmfs_amd.bank        feature-bank builders + the RCCL all-gather of image features
     mmfs_amd.sequence    the interleaved sequence: embeddings with the visual rows and <soi> in place, the image decoder's
                          per-image context, the special-token tables both read
+    mmfs_amd.text_loss   the end of the training step: the labels, the cross-entropy of the text decoder's 16-bit logits and
+                         its gradient in three passes over the logits, the per-option scores (the package attribute
+                         ``text_loss`` is the function; ``from mmfs_amd.text_loss import ..`` reaches the module)
 """
 from .functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch  # noqa: F401
 from .levels import invalidate_caches  # noqa: F401
 from .sequence import (SequenceTables, assemble_mm_embeds, prepare_context_features_for_image_decoder,  # noqa: F401
                        sequence_tables, sincos_1d_table)
+from .text_loss import option_scores, prepare_gt_text_ids, text_loss  # noqa: F401
 
 __version__ = "0.1.0"
