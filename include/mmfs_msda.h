@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_text_loss_supported / _forward / _backward, MMFS_TEXT_LOSS_*: the text loss (cross-entropy of
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_qk_attn_supported / _forward / _backward: the Q-Former's attention with per-head q/k
+                                   *     LayerNorm as one forward and one backward kernel, see "Q-Former attention" below
+                                   * 14 (additive): + mmfs_text_loss_supported / _forward / _backward, MMFS_TEXT_LOSS_*: the text loss (cross-entropy of
                                    *     the text decoder's 16-bit logits and its gradient) on the device, see "The text loss" below
                                    * 14 (additive): + mmfs_sequence_supported / _index / _embed_forward / _embed_backward / _context_forward /
                                    *     _context_backward_workspace_bytes / _context_backward: the interleaved sequence (embeddings and the image
@@ -779,6 +781,46 @@ int mmfs_text_loss_forward(int dtype, const void *logits, const int64_t *labels,
 int mmfs_text_loss_backward(int dtype, const void *logits, const int64_t *labels, const float *lse, const float *upstream,
                             const int32_t *counts, void *grad, int64_t B, int64_t L, int64_t V, int64_t first, int64_t n,
                             int64_t ignore_index, int reduction, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Q-Former attention with per-head q/k LayerNorm (csrc/mmfs_attn.hip; additive at ABI 14).  Replaces, between the three Linear
+ * layers of the reference's patched Blip2QFormerMultiHeadAttention and its output
+ * (mm_interleaved/models/utils/monkey_patch/blip2_qknorm_monkey_patch.py:76-147), the three permuted views, the LayerNorm over
+ * the 64 channels of every head of q and of k, q k^T / 8 + mask, the softmax over a [B, H, Nq, Nk] tensor, p v and the permuted
+ * copy back.  No entry reads anything back, allocates, clears or synchronises: all of them can be captured into a graph.
+ *   q [B, Nq, H * 64], k, v [B, Nk, H * 64] of T (MMFS_F16 / MMFS_BF16), packed, as the Linear layers return them
+ *   q_norm_weight, q_norm_bias, k_norm_weight, k_norm_bias [64] of ``norm_dtype`` (MMFS_F32 or ``dtype``) with ``eps``: all
+ *       four or none (no normalisation)
+ *   key_bias [B, Nk] (``bias_stride`` = Nk) or [Nk] shared by the batch (``bias_stride`` = 0) of ``bias_dtype`` (MMFS_F32 or
+ *       ``dtype``), or NULL: added to the scaled scores (HF's extended mask [B, 1, 1, Nk]); not differentiated.  A bias at or
+ *       below finfo(T).min marks a masked key: its score IS the bias, as the framework's sum in T leaves it
+ * mmfs_qk_attn_supported: D == 64, 1 <= Nq <= 128, 1 <= Nk <= 8192, a 16-bit type; otherwise 0, the calls return
+ * MMFS_E_UNSUPPORTED and the caller keeps the framework's statement (fp32 storage, other head widths, more queries).
+ * mmfs_qk_attn_forward: one launch, B * H workgroups.
+ *   context [B, Nq, H * 64] of T    softmax_k(q^ . k^ / 8 + key_bias) v, q^ / k^ the normalised rows rounded to T; every element
+ *                                   written once.  Keys at finfo(T).min only: the uniform average; at -Inf only: NaN
+ *   lse   [B, H, Nq]    fp32        log sum_k exp(score)
+ *   stats [B, H, Nq, 2] fp32        (row maximum m, l = sum_k exp(score - m)): what the backward reads
+ * mmfs_qk_attn_backward: one launch (two with the LayerNorms).  grad_q, grad_k, grad_v of T: every element written exactly once,
+ *   no atomics: bit-reproducible.  partials [B * H, 4, 64] fp32 (workspace, every element written) and grad_params [4, 64] fp32 =
+ *   d(q_norm_weight), d(q_norm_bias), d(k_norm_weight), d(k_norm_bias), summed over the workgroups in ascending order; both
+ *   unused and may be NULL without the LayerNorms.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code; a ``norm_dtype`` / ``bias_dtype`` of a given tensor that is
+ * neither MMFS_F32 nor ``dtype``); MMFS_E_DIMS for a negative size, B * H > 2^24 or a ``bias_stride`` that is neither 0 nor Nk;
+ * MMFS_E_UNSUPPORTED for what the query refuses; MMFS_E_NULLPTR for a NULL required pointer of a non-empty problem or some but
+ * not all of the four LayerNorm pointers; MMFS_E_ALIGN for q, k, v, context and the gradients that are not 16-byte aligned
+ * (the small tensors and the fp32 ones: their element size). */
+int mmfs_qk_attn_supported(int dtype, int64_t D, int64_t Nq, int64_t Nk);
+int mmfs_qk_attn_forward(int dtype, const void *q, const void *k, const void *v, const void *q_norm_weight,
+                         const void *q_norm_bias, const void *k_norm_weight, const void *k_norm_bias, int norm_dtype, float eps,
+                         const void *key_bias, int bias_dtype, int64_t bias_stride, void *context, float *lse, float *stats,
+                         int64_t B, int64_t H, int64_t D, int64_t Nq, int64_t Nk, void *stream);
+int mmfs_qk_attn_backward(int dtype, const void *q, const void *k, const void *v, const void *q_norm_weight,
+                          const void *q_norm_bias, const void *k_norm_weight, const void *k_norm_bias, int norm_dtype, float eps,
+                          const void *key_bias, int bias_dtype, int64_t bias_stride, const void *context,
+                          const void *grad_context, const float *stats, void *grad_q, void *grad_k, void *grad_v,
+                          float *partials, float *grad_params, int64_t B, int64_t H, int64_t D, int64_t Nq, int64_t Nk,
+                          void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

@@ -13,9 +13,12 @@ and the callers either side of the op:
     mmfs_amd.text_loss   the end of the training step: the labels, the cross-entropy of the text decoder's 16-bit logits and
                          its gradient in three passes over the logits, the per-option scores (the package attribute
                          ``text_loss`` is the function; ``from mmfs_amd.text_loss import ..`` reaches the module)
+    mmfs_amd.resampler   QKNormAttention: the Perceiver resampler's Q-Former attention with per-head q/k LayerNorm, fused
 """
 from .functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch  # noqa: F401
+from .functions import QKNormAttentionFunction, qk_attn_supported  # noqa: F401
 from .levels import invalidate_caches  # noqa: F401
+from .resampler import QKNormAttention  # noqa: F401
 from .sequence import (SequenceTables, assemble_mm_embeds, prepare_context_features_for_image_decoder,  # noqa: F401
                        sequence_tables, sincos_1d_table)
 from .text_loss import option_scores, prepare_gt_text_ids, text_loss  # noqa: F401

@@ -7,3 +7,4 @@ from .deform_plan_func import DeformPlanFunction, deform_plan_supported, deform_
 from .dwconv_func import DWConvTokensFunction, dwconv_tokens_supported  # noqa: F401,E402
 from .pyramid_func import PyramidHeadFunction, pyramid_head_supported  # noqa: F401,E402
 from .sequence_func import ContextGatherFunction, SequenceEmbedFunction, sequence_supported  # noqa: F401,E402
+from .qk_attn_func import QKNormAttentionFunction, qk_attn_supported  # noqa: F401,E402
