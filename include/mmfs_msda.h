@@ -36,7 +36,10 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_qk_attn_supported / _forward / _backward: the Q-Former's attention with per-head q/k
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_llama_attn_supported / _rope_append / _decode_keys / _decode_workspace_bytes / _decode: the LLM's self-attention
+                                   *     at decode (rotary embedding, in-place key / value cache, split-key attention), see "LLaMA self-attention at
+                                   *     decode" below
+                                   * 14 (additive): + mmfs_qk_attn_supported / _forward / _backward: the Q-Former's attention with per-head q/k
                                    *     LayerNorm as one forward and one backward kernel, see "Q-Former attention" below
                                    * 14 (additive): + mmfs_text_loss_supported / _forward / _backward, MMFS_TEXT_LOSS_*: the text loss (cross-entropy of
                                    *     the text decoder's 16-bit logits and its gradient) on the device, see "The text loss" below
@@ -821,6 +824,57 @@ int mmfs_qk_attn_backward(int dtype, const void *q, const void *k, const void *v
                           const void *grad_context, const float *stats, void *grad_q, void *grad_k, void *grad_v,
                           float *partials, float *grad_params, int64_t B, int64_t H, int64_t D, int64_t Nq, int64_t Nk,
                           void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * LLaMA self-attention at decode (csrc/mmfs_llama_attn.hip; additive at ABI 14).  Replaces, between the three Linear layers of the
+ * reference's LlamaAttention and its o_proj (mm_interleaved/models/decoders/modeling_llama_mmfs.py:217-280), the rotary embedding
+ * (:165-172), the torch.cat that grows the cache (:241-242), the [B, H, 1, T] scores, their clamp, softmax and second product
+ * (:246-264), and under beam search the index_select of the whole cache (:913-917).  No entry reads anything back, allocates,
+ * clears or synchronises: all of them can be captured into a graph.
+ *   k_cache, v_cache [B, H, cap, 128] of T (MMFS_F16 / MMFS_BF16): one layer's keys (rotated) and values, written in place
+ *   length   [1] int32      device word: the tokens the cache holds, the same for every row; the CALLER adds to it after the last
+ *                           layer of a step (the entries read it, none writes it)
+ *   src_row  [B, cap] int32 the physical batch row that holds logical row b's token t: the append writes b; a beam reorder
+ *                           permutes its rows (B * cap ints) in place of the cache
+ * mmfs_llama_attn_supported: D == 128, a 16-bit type, 1 <= Lq <= cap <= 2^22; otherwise 0, the calls return MMFS_E_UNSUPPORTED
+ * and the caller keeps the framework's statement.
+ * mmfs_llama_attn_rope_append: one launch.  q, k, v [B, Lq, H * 128] of T, packed, as the Linear layers return them; position_ids
+ *   [B, Lq] int64; cos_table, sin_table [max_pos, 64] fp32 (host-made, as FixedLlamaRotaryEmbedding makes them).
+ *   q_rot [B, Lq, H * 128] = q cos + rotate_half(q) sin (channel pairs (i, i + 64), fp32, one rounding); the same of k and v as it
+ *   is go to slots length + j, j < Lq, of physical row b, and src_row[b, length + j] = b.  A position outside [0, max_pos) reads no
+ *   table entry and makes that token's q and k NaN.  The caller guarantees length + Lq <= cap; a slot outside the cache is not
+ *   written.
+ * mmfs_llama_attn_decode: Lq = 1, two launches (the split walk of the keys, the merge of its partials in ascending order).
+ *   context [B, 1, H * 128] of T = softmax_t(q_rot . K[src_row[b, t], h, t] / sqrt(128) + bias[b, t]) V over the keys
+ *   t < length + 1 (the slot the append of this step wrote included).
+ *   bias [B, bias_len] with rows ``bias_stride`` apart, or one shared row (``bias_stride`` = 0), of ``bias_dtype`` (MMFS_F32 or
+ *       ``dtype``), or NULL: HF's extended mask [B, 1, 1, kv_len] without its broadcast axes; keys at or behind bias_len have
+ *       none.  A bias at or below finfo(T).min marks a masked key: its score IS the bias, as the reference's sum and clamp in T
+ *       leave it; keys that are all masked give the uniform average of their values
+ *   kv_bound  a HOST upper bound of length + 1, <= cap: the grid is cut from it (256 keys a workgroup), never from the device
+ *       word, and workgroups behind the length return at once, so a step captured at one length replays at any later length
+ *       up to kv_bound.  Results do not depend on it.  A length + 1 outside [1, kv_bound] gives NaN
+ *   workspace  mmfs_llama_attn_decode_workspace_bytes(B, H, kv_bound) bytes (< 0: MMFS_E_DIMS), 16-byte aligned: the partials;
+ *       nothing in it needs clearing
+ *   No atomics: bit-reproducible, eager or replayed.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code; a ``bias_dtype`` of a given bias that is neither MMFS_F32 nor
+ * ``dtype``); MMFS_E_DIMS for a negative size, B * H > 2^24, kv_bound outside [1, cap], a bias_stride that is neither 0 nor at
+ * least bias_len; MMFS_E_UNSUPPORTED for what the query refuses; MMFS_E_NULLPTR for a NULL required pointer of a non-empty
+ * problem; MMFS_E_ALIGN for q, k, v, q_rot, the caches, the tables, context and the workspace that are not 16-byte aligned
+ * (position_ids, length, src_row and the bias: their element size). */
+int mmfs_llama_attn_supported(int dtype, int64_t D, int64_t Lq, int64_t cap);
+int mmfs_llama_attn_rope_append(int dtype, const void *q, const void *k, const void *v, const int64_t *position_ids,
+                                const float *cos_table, const float *sin_table, int64_t max_pos, const int32_t *length,
+                                void *q_rot, void *k_cache, void *v_cache, int32_t *src_row, int64_t B, int64_t Lq, int64_t H,
+                                int64_t D, int64_t cap, void *stream);
+/* the decode walk's cut of the keys, for callers and tests that want its edges: level 0 the keys of a wave, level 1 the keys of a
+ * workgroup, which is a split; any other level MMFS_E_DIMS.  Host-only. */
+int64_t mmfs_llama_attn_decode_keys(int level);
+int64_t mmfs_llama_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_t kv_bound);
+int mmfs_llama_attn_decode(int dtype, const void *q_rot, const void *k_cache, const void *v_cache, const int32_t *src_row,
+                           const int32_t *length, const void *bias, int bias_dtype, int64_t bias_stride, int64_t bias_len,
+                           void *context, float *workspace, int64_t B, int64_t H, int64_t D, int64_t cap, int64_t kv_bound,
+                           void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.
