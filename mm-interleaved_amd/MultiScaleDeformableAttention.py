@@ -21,6 +21,7 @@ There is NO CPU or PyTorch fallback: CPU tensors raise, exactly as the reference
 does (src/ms_deform_attn.h:29-38: "Not implemented on the CPU"), and a missing
 shared library raises at import time.
 """
+import collections
 import ctypes
 import os
 
@@ -139,6 +140,12 @@ def _require(cond, msg):
         raise RuntimeError(msg)
 
 
+def _check_step(B, im2col_step):
+    # the reference walks the batch im2col_step rows at a time (.cu:51-53); the kernels here take it whole
+    step = min(B, int(im2col_step)) if B > 0 else 1
+    _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
+
+
 def _validate(named, value):
     # (messages are only built when a check fails: this runs on every call of a ~100 us step)
     dev = value.device
@@ -249,6 +256,15 @@ class _on_device:
 # host-only size queries of the library, memoised (they depend on the numbers only; the level table enters
 # through the identity + version of its host copy)
 _ws_cache = {}
+
+
+def _memo(key, ask):
+    n = _ws_cache.get(key)
+    if n is None:
+        if len(_ws_cache) > 4096:
+            _ws_cache.clear()
+        n = _ws_cache[key] = ask()
+    return n
 
 
 # bench.py sets this to a list to time individual kernels with HIP events recorded on
@@ -387,8 +403,7 @@ def _forward_fp8(value, value_scale, spatial_shapes, level_start_index, sampling
         B, S, H, D, L, Nq, P, Bv = _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                                                 value_repeat)
         layout = _VALUE_REPEAT[value_repeat]
-    step = min(B, int(im2col_step)) if B > 0 else 1
-    _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
+    _check_step(B, im2col_step)
     dt = attn_weight.dtype
     _require(dt in (torch.float32, torch.float16, torch.bfloat16), f"fp8 bank: unsupported output dtype {dt}")
     _require(value_scale.dtype == torch.float32 and tuple(value_scale.shape) == (value.shape[0], H * D),
@@ -436,8 +451,7 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     else:
         B, S, H, D, L, Nq, P, Bv = _dims_shared(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                                                 value_repeat)
-    step = min(B, int(im2col_step)) if B > 0 else 1
-    _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
+    _check_step(B, im2col_step)
     sampling_loc, attn_weight = _same_dtype(value, sampling_loc, attn_weight)
     value = _aligned(value)
     out = torch.empty((B, Nq, H * D), dtype=value.dtype, device=value.device)
@@ -501,48 +515,6 @@ _bwd_algo = "auto"
 # (True: levels of at most min(256, 64*P) pixels take the matrix-core product, csrc/msda_dense.hip)
 _hybrid = os.environ.get("MMFS_HYBRID", "1") != "0"
 
-# The backward's two halves are independent (grad_loc / grad_attn read value; grad_value does not)
-# and can be launched on two streams (a side stream that forks from and joins the caller's stream
-# inside the call).  Measured on MI355X: both halves already fill the chip, so they mostly
-# time-share: -1.2 % step time at the north-star shape, -3 % at the SD geometry, but +15 % at
-# config 1, where the step is host-bound and the extra stream calls cost more than they hide.
-# Off by default; MMFS_BWD_OVERLAP=1 turns it on.
-_bwd_overlap = os.environ.get("MMFS_BWD_OVERLAP", "0") == "1"
-_side_streams = {}
-
-
-def _side_stream(device):
-    st = _side_streams.get(device)
-    if st is None:
-        st = _side_streams[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-class _fork:
-    """with _fork(device) as side: launches inside go to the side stream (None: overlap off)."""
-
-    def __init__(self, device):
-        self.device, self.side, self.ctx = device, None, None
-
-    def __enter__(self):
-        if _bwd_overlap:
-            self.main = torch.cuda.current_stream(self.device)
-            self.side = _side_stream(self.device)
-            self.side.wait_stream(self.main)
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
-
-    def join(self):
-        if self.side is not None:
-            self.main.wait_stream(self.side)
-
-
 # stage bits of mmfs_msda_backward_sorted (include/mmfs_msda.h)
 _SRT_BWD_STAGES = (("msda_bwd_value_prepare", 1), ("msda_bwd_value_sort", 2), ("msda_bwd_taps", 4), ("msda_bwd_value_reduce", 8))
 _SRT_BWD_ALL = 15
@@ -551,6 +523,15 @@ _SRT_BWD_ALL = 15
 _HYB_BWD_STAGES = (("msda_bwd_taps", 1), ("msda_bwd_taps_coarse", 2), ("msda_bwd_value_prepare", 4),
                    ("msda_bwd_value_sort", 8), ("msda_bwd_value_reduce", 16))
 _HYB_BWD_ALL = 31
+
+# the library's own sequence on a canonical table, one entry point per kernel
+_STAGED_BWD = (("msda_bwd_taps", "mmfs_msda_backward_taps"), ("msda_bwd_value_prepare", "mmfs_msda_backward_value_prepare"),
+               ("msda_bwd_value_sort", "mmfs_msda_backward_value_sort"), ("msda_bwd_value_reduce", "mmfs_msda_backward_value_reduce"))
+_LIBRARY_BWD = (("msda_bwd_atomic", "mmfs_msda_backward_checked"),)
+# which of the backward's pointers -- value, shapes, start, loc, attn, grad_out, grad_value, grad_loc, grad_attn: 0 .. 8 -- each
+# of the per-kernel entry points takes, and whether (workspace, workspace_bytes) follow them
+_STAGED_ARGS = {"mmfs_msda_backward_taps": ((0, 1, 2, 3, 4, 5, 7, 8), False), "mmfs_msda_backward_value_prepare": ((3, 4), True),
+                "mmfs_msda_backward_value_sort": ((1, 2), True), "mmfs_msda_backward_value_reduce": ((5, 6), True)}
 
 
 def levels_are_canonical(spatial_shapes, level_start_index, S):
@@ -617,6 +598,74 @@ def register_level_tables(spatial_shapes, level_start_index, S, host_shapes=None
     return _seed_level_info(spatial_shapes, key, sh, st, S)
 
 
+
+
+# What one backward call does, decided from numbers alone (_backward_plan):
+#   route        "sorted" (mmfs_msda_backward_sorted) | "hybrid" (mmfs_msda_backward_hybrid) | "staged" (the library's own
+#                sequence, one entry point per kernel) | "library" (that sequence in one call of mmfs_msda_backward_checked)
+#   flags        of mmfs_msda_backward, as every call of the route passes them
+#   ws_bytes     of the route's workspace
+#   stages       what to launch, in order: (name in the event log, stage bits for "sorted" / "hybrid", else the entry point)
+#   blocks4      4x4 pixel blocks of the table ("sorted" only)
+#   status_word  whether the call is handed the device's status word (a table the device has to check)
+_BackwardPlan = collections.namedtuple("_BackwardPlan", "route flags ws_bytes stages blocks4 status_word")
+
+
+def _backward_plan(code, dims, slab_bytes, info, lazy_zero_attn):
+    """The route of a backward of type ``code`` and ``dims`` = (B, S, H, D, L, Nq, P): no tensor is looked at.
+    ``slab_bytes``: one batch row of value; ``info``: what ``_level_info`` knows about the level table, or None.
+    Reads the knobs (_taps_algo, _taps_prefer_sorted, _bwd_algo, _hybrid) and, for "one call or one per kernel",
+    _event_log; asks the library's host-only queries through ``_memo``."""
+    per_kernel = _event_log is not None
+    over_limit = slab_bytes > _MAX_SLAB_BYTES
+    # (as the forward: the LDS-levels kernel named for a value slab its 32-bit row offsets cannot span -- a matter of
+    # size, so the call goes to the row gather's flat-address kernel instead of raising)
+    taps = "gather" if _taps_algo == "lds" and over_limit else _taps_algo
+    flags = (_BWD_LAZY_ZERO_ATTN if lazy_zero_attn else 0) | _TAPS_FLAGS[taps]
+    if _bwd_algo == "atomic":
+        flags |= _BWD_FORCE_ATOMIC
+    elif info is None:
+        flags |= _BWD_DEVICE_CHECKED_LEVELS
+    elif info[0]:
+        flags |= _BWD_CANONICAL_LEVELS
+    canonical = bool(flags & _BWD_CANONICAL_LEVELS)                 # a table the HOST has verified
+    # opt-in: grad_loc / grad_attn from the grad_value sort's records (csrc/msda_bwd_taps_sorted.hip): a host-verified
+    # canonical table, 16-bit storage, shapes the sort's kept scan takes
+    if (_taps_algo == "sorted" or (_taps_prefer_sorted and _taps_algo == "auto")) and canonical and code in (1, 2):
+        srt_bytes = _memo(("sorted", code, dims, flags),
+                          lambda: _lib.mmfs_msda_backward_sorted_workspace_bytes(code, *dims, flags))
+        if srt_bytes > 0:
+            return _BackwardPlan("sorted", flags, srt_bytes, _SRT_BWD_STAGES if per_kernel else (("msda_bwd", _SRT_BWD_ALL),),
+                                 host_level_counts(info[1])[0], False)
+    # ("sorted" by name raises where the route does not apply -- except for a value slab over the limit: the call then
+    # goes on to the routes below, like the other named kernels'.  Decided on the size alone, whatever else the route
+    # would have refused: fp32 storage, an unregistered or non-canonical table, the float-atomic route asked for.)
+    _require(_taps_algo != "sorted" or over_limit,
+             "taps algo 'sorted': mmfs_msda_backward_sorted does not apply to these arguments")
+    if _hybrid and canonical and code in (1, 2):
+        # small levels on the matrix cores, the others through the gather / sort / reduce kernels
+        flags |= _BWD_DENSE_TAPS
+        # (keyed by the table's CONTENT: a freed host copy's address can come back with another table)
+        hyb_bytes = _memo((code, dims, flags, info[1].tobytes(), info[2].tobytes()),
+                          lambda: _lib.mmfs_msda_backward_hybrid_workspace_bytes(code, info[1].ctypes.data, info[2].ctypes.data,
+                                                                                 *dims, flags))
+        if hyb_bytes > 0:
+            stages = (("msda_bwd", _HYB_BWD_ALL),)
+            if per_kernel:
+                stages = _HYB_BWD_STAGES
+                # (one kernel does every level: the dense stage has nothing to launch)
+                if _memo(("fused", code, dims, flags), lambda: _lib.mmfs_msda_backward_taps_fused(code, *dims, flags)):
+                    stages = tuple(s for s in stages if s[0] != "msda_bwd_taps_coarse")
+            return _BackwardPlan("hybrid", flags, hyb_bytes, stages, 0, False)
+    # the library's own sequence: taps + sort + reduce when the level table is canonical and the head width has a vector
+    # path, else (odd head width, fp64, gapped or overlapping levels) float-atomic accumulation (needs an fp32 scratch for
+    # 16-bit storage).  One call, unless each kernel is to be timed and the host knows that the table is canonical.
+    ws_bytes = _memo((code, dims, flags), lambda: _lib.mmfs_msda_backward_workspace_bytes(code, *dims, flags))
+    if canonical and per_kernel:
+        return _BackwardPlan("staged", flags, ws_bytes, _STAGED_BWD, 0, False)
+    return _BackwardPlan("library", flags, ws_bytes, _LIBRARY_BWD, 0, bool(flags & _BWD_DEVICE_CHECKED_LEVELS))
+
+
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                             grad_output, im2col_step, lazy_zero_attn=False, *, value_repeat=None):
     """Reference: ms_deform_attn_cuda_backward, src/cuda/ms_deform_attn_cuda.cu:84-166.
@@ -648,172 +697,64 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     _validate([("value", value), ("spatial_shapes", spatial_shapes),
                ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                ("attn_weight", attn_weight), ("grad_output", grad_output)], value)
-    B, S, H, D, L, Nq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+    B, S, H, D, L, Nq, P = dims = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     _require(grad_output.numel() == B * Nq * H * D, "grad_output must be [B, Nq, H*D]")
-    step = min(B, int(im2col_step)) if B > 0 else 1
-    _require(step > 0 and B % step == 0, f"batch({B}) must divide im2col_step({step})")
+    _check_step(B, im2col_step)
     loc_dtype, attn_dtype = sampling_loc.dtype, attn_weight.dtype
     sampling_loc, attn_weight = _same_dtype(value, sampling_loc, attn_weight)
     if grad_output.dtype != value.dtype:
         grad_output = grad_output.to(value.dtype)
     value, grad_output = _aligned(value), _aligned(grad_output)
-
-    dt = value.dtype
+    dt, dev = value.dtype, value.device
     code = _DTYPE_CODE[dt]
-    dims = (B, S, H, D, L, Nq, P)
-    taps = _taps_algo
-    if taps == "lds" and S * H * D * value.element_size() > _MAX_SLAB_BYTES:
-        # (as the forward: the LDS-levels kernel named for a value slab its 32-bit row offsets cannot span -- a matter of
-        # size, so the call goes to the row gather's flat-address kernel instead of raising)
-        taps = "gather"
-    flags = (_BWD_LAZY_ZERO_ATTN if lazy_zero_attn else 0) | _TAPS_FLAGS[taps]
-    info = None
-    if _bwd_algo == "atomic":
-        flags |= _BWD_FORCE_ATOMIC
-    else:
-        # What the level tables contain is only looked up, never fetched: tables that came from
-        # mmfs_amd.levels.make_level_tables / register_level_tables (or were seen by levels_are_canonical)
-        # carry their host copy; for any other pair -- the reference's own callers build fresh tensors on
-        # every call -- the library checks the table on the device (no device->host copy, no sync).
-        info = _level_info(spatial_shapes, level_start_index, S, sync=False)
-        if info is None:
-            flags |= _BWD_DEVICE_CHECKED_LEVELS
-        elif info[0]:
-            flags |= _BWD_CANONICAL_LEVELS
-    grad_value = torch.empty(value.shape, dtype=dt, device=value.device)
-    grad_loc = torch.empty(sampling_loc.shape, dtype=dt, device=value.device)
-    grad_attn = torch.empty(attn_weight.shape, dtype=dt, device=value.device)
-    with _on_device(value.device):
-        stream = _stream(value.device)
-        status = _E_UNSUPPORTED
-        hyb_bytes = 0
-        # opt-in: grad_loc / grad_attn from the grad_value sort's records (csrc/msda_bwd_taps_sorted.hip): a host-verified
-        # canonical table, 16-bit storage, shapes the sort's kept scan takes
-        srt_bytes = 0
-        if (_taps_algo == "sorted" or (_taps_prefer_sorted and _taps_algo == "auto")) and _bwd_algo != "atomic" and info is not None and (flags & _BWD_CANONICAL_LEVELS) and code in (1, 2):
-            skey = ("sorted", code, dims, flags)
-            srt_bytes = _ws_cache.get(skey)
-            if srt_bytes is None:
-                if len(_ws_cache) > 4096:
-                    _ws_cache.clear()
-                srt_bytes = _ws_cache[skey] = _lib.mmfs_msda_backward_sorted_workspace_bytes(code, *dims, flags)
-        # ("sorted" by name raises where the route does not apply -- except for a value slab over the limit: the call then
-        # goes on to the routes below, like the other named kernels'.  Decided here, on the size alone, whatever else the
-        # route would have refused -- fp32 storage, an unregistered or non-canonical table, the float-atomic route asked for --:
-        # in those cases srt_bytes is 0 without the library having been asked.)
-        _require(srt_bytes > 0 or _taps_algo != "sorted" or S * H * D * value.element_size() > _MAX_SLAB_BYTES,
-                 "taps algo 'sorted': mmfs_msda_backward_sorted does not apply to these arguments")
-        if srt_bytes > 0:
-            route_counts["sorted"] += 1
-            ws = torch.empty(srt_bytes, dtype=torch.uint8, device=value.device)
-            blocks4 = host_level_counts(info[1])[0]
-            sargs = (code, value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                     sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                     grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), ws.data_ptr(), srt_bytes,
-                     *dims, blocks4, flags)
-            if _event_log is None:
-                status = _lib.mmfs_msda_backward_sorted(*sargs, _SRT_BWD_ALL, stream)
-            else:
-                for name, bit in _SRT_BWD_STAGES:
-                    status = _launch(name, value.device, _lib.mmfs_msda_backward_sorted, *sargs, bit, _stream(value.device))
-                    if status != 0:
-                        break
-            _check(status, "ms_deform_attn_backward")
-            if loc_dtype != dt:
-                grad_loc = grad_loc.to(loc_dtype)
-            if attn_dtype != dt:
-                grad_attn = grad_attn.to(attn_dtype)
-            return [grad_value, grad_loc, grad_attn]
-        if _hybrid and info is not None and (flags & _BWD_CANONICAL_LEVELS) and code in (1, 2):
-            flags |= _BWD_DENSE_TAPS
-            hs, hst = info[1].ctypes.data, info[2].ctypes.data
-            # (keyed by the table's CONTENT: a freed host copy's address can come back with another table)
-            key = (code, dims, flags, info[1].tobytes(), info[2].tobytes())
-            hyb_bytes = _ws_cache.get(key)
-            if hyb_bytes is None:
-                if len(_ws_cache) > 4096:
-                    _ws_cache.clear()
-                hyb_bytes = _ws_cache[key] = _lib.mmfs_msda_backward_hybrid_workspace_bytes(code, hs, hst, *dims, flags)
-        if hyb_bytes > 0:
-            # small levels on the matrix cores, the others through the gather / sort / reduce kernels
-            ws = torch.empty(hyb_bytes, dtype=torch.uint8, device=value.device)
-            args = (code, value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), hs, hst,
-                    sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                    grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), ws.data_ptr(), hyb_bytes,
-                    *dims, flags)
-            fkey = ("fused", code, dims, flags)
-            fused = _ws_cache.get(fkey)
-            if fused is None:
-                fused = _ws_cache[fkey] = _lib.mmfs_msda_backward_taps_fused(code, *dims, flags)
-            sorted_levels = host_level_counts(info[1])[1]
 
-            def run_stages(stages):
-                st = 0
-                if fused:               # one kernel does every level: the dense stage has nothing to launch
-                    stages = tuple(sb for sb in stages if sb[0] != "msda_bwd_taps_coarse")
-                if sorted_levels == 0:
-                    stages = tuple(sb for sb in stages if sb[0] not in ("msda_bwd_value_prepare", "msda_bwd_value_sort",
-                                                                        "msda_bwd_value_reduce"))
-                if _event_log is None:
-                    bits = sum(bit for _, bit in stages)
-                    return _lib.mmfs_msda_backward_hybrid(*args, bits, _stream(value.device))
-                for name, bit in stages:
-                    st = _launch(name, value.device, _lib.mmfs_msda_backward_hybrid, *args, bit, _stream(value.device))
-                    if st != 0:
-                        break
-                return st
-            if _event_log is None and not _bwd_overlap:
-                status = _lib.mmfs_msda_backward_hybrid(*args, _HYB_BWD_ALL, stream)    # one call, one stream
-            else:
-                fork = _fork(value.device)
-                with fork:
-                    status = run_stages(_HYB_BWD_STAGES[:2])         # grad_loc / grad_attn (side stream)
-                if status == 0:
-                    status = run_stages(_HYB_BWD_STAGES[2:])         # grad_value
-                fork.join()
-        ws_bytes = 0
-        if hyb_bytes == 0:
-            key = (code, dims, flags)
-            ws_bytes = _ws_cache.get(key)
-            if ws_bytes is None:
-                if len(_ws_cache) > 4096:
-                    _ws_cache.clear()
-                ws_bytes = _ws_cache[key] = _lib.mmfs_msda_backward_workspace_bytes(code, *dims, flags)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device) if ws_bytes else None
-        ws_ptr = ws.data_ptr() if ws is not None else None
-        if hyb_bytes == 0 and (flags & (_BWD_CANONICAL_LEVELS | _BWD_DEVICE_CHECKED_LEVELS)) and _event_log is None and not _bwd_overlap:
-            pass                                 # the library's own sequence below: one call (same kernels)
-        elif hyb_bytes == 0 and (flags & _BWD_CANONICAL_LEVELS):
-            # sorted backward, stage by stage (so each kernel can be timed / the halves can overlap)
-            fork = _fork(value.device)
-            with fork:
-                status = _launch("msda_bwd_taps", value.device, _lib.mmfs_msda_backward_taps, code,
-                                 value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                 sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                                 grad_loc.data_ptr(), grad_attn.data_ptr(), *dims, _stream(value.device))
-            if status == 0:
-                status = _launch("msda_bwd_value_prepare", value.device, _lib.mmfs_msda_backward_value_prepare,
-                                 code, sampling_loc.data_ptr(), attn_weight.data_ptr(), ws_ptr, ws_bytes,
-                                 *dims, stream)
-            if status == 0:
-                status = _launch("msda_bwd_value_sort", value.device, _lib.mmfs_msda_backward_value_sort, code,
-                                 spatial_shapes.data_ptr(), level_start_index.data_ptr(), ws_ptr, ws_bytes,
-                                 *dims, stream)
-            if status == 0:
-                status = _launch("msda_bwd_value_reduce", value.device, _lib.mmfs_msda_backward_value_reduce,
-                                 code, grad_output.data_ptr(), grad_value.data_ptr(), ws_ptr, ws_bytes,
-                                 *dims, stream)
-            fork.join()
-        if status == _E_UNSUPPORTED:
-            # the library's own sequence: taps + sort + reduce when the level table is canonical and
-            # the head width has a vector path, else (odd head width, fp64, gapped or overlapping
-            # levels) float-atomic accumulation (needs an fp32 scratch for 16-bit storage)
-            word = _status_word(value.device)[0].data_ptr() if (flags & _BWD_DEVICE_CHECKED_LEVELS) else None
-            status = _launch("msda_bwd_atomic", value.device, _lib.mmfs_msda_backward_checked, code,
-                             value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                             sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                             grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
-                             ws_ptr, ws_bytes, *dims, flags, word, stream)
+    # What the level tables contain is only looked up, never fetched: tables that came from
+    # mmfs_amd.levels.make_level_tables / register_level_tables (or were seen by levels_are_canonical)
+    # carry their host copy; for any other pair -- the reference's own callers build fresh tensors on
+    # every call -- the library checks the table on the device (no device->host copy, no sync).
+    info = _level_info(spatial_shapes, level_start_index, S, sync=False)
+    plan = _backward_plan(code, dims, S * H * D * value.element_size(), info, lazy_zero_attn)
+
+    grad_value = torch.empty(value.shape, dtype=dt, device=dev)
+    grad_loc = torch.empty(sampling_loc.shape, dtype=dt, device=dev)
+    grad_attn = torch.empty(attn_weight.shape, dtype=dt, device=dev)
+    workspace = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=dev) if plan.ws_bytes else None
+    ws = (workspace.data_ptr() if workspace is not None else None, plan.ws_bytes)
+    # the pointers every entry point takes some of, in the order of mmfs_msda_backward (include/mmfs_msda.h)
+    ptrs = (value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+            attn_weight.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr())
+    if plan.route == "sorted":
+        route_counts["sorted"] += 1
+    with _on_device(dev):
+        stream = _stream(dev)
+        word = _status_word(dev)[0].data_ptr() if plan.status_word else None
+
+        tables = (info[1].ctypes.data, info[2].ctypes.data) if plan.route == "hybrid" else None
+
+        def call(stage, ws):
+            """(entry point, its arguments between the type code and the stream) of one stage: ``stage`` is the stage bits
+            of the plan's route, or the name of an entry point of the library's own sequence."""
+            if stage == "mmfs_msda_backward_checked":
+                return stage, (*ptrs, *ws, *dims, plan.flags, word)
+            if plan.route == "sorted":
+                return "mmfs_msda_backward_sorted", (*ptrs, *ws, *dims, plan.blocks4, plan.flags, stage)
+            if plan.route == "hybrid":
+                return "mmfs_msda_backward_hybrid", (*ptrs[:3], *tables, *ptrs[3:], *ws, *dims, plan.flags, stage)
+            take, with_ws = _STAGED_ARGS[stage]
+            return stage, (*[ptrs[i] for i in take], *(ws if with_ws else ()), *dims)
+
+        def run(stages, ws):
+            for name, stage in stages:
+                entry, args = call(stage, ws)
+                status = _launch(name, dev, getattr(_lib, entry), code, *args, stream)
+                if status != 0:
+                    return status
+            return 0
+        status = run(plan.stages, ws)
+        if status == _E_UNSUPPORTED and plan.route in ("hybrid", "staged"):
+            # refused, so fall back: the library's one call with the flags the route had (_BWD_DENSE_TAPS included) and the
+            # workspace that was asked about -- none in the hybrid route's case, where only the hybrid workspace was
+            status = run(_LIBRARY_BWD, ws if plan.route == "staged" else (None, 0))
         _check(status, "ms_deform_attn_backward")
     if loc_dtype != dt:
         grad_loc = grad_loc.to(loc_dtype)
