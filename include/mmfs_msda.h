@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_llama_attn_supported / _rope_append / _decode_keys / _decode_workspace_bytes / _decode: the LLM's self-attention
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_llama_attn_prefill / _prefill_tiles, MMFS_LLAMA_PREFILL_*: the same attention over a prompt, see
+                                   *     "LLaMA self-attention over a prompt" below
+                                   * 14 (additive): + mmfs_llama_attn_supported / _rope_append / _decode_keys / _decode_workspace_bytes / _decode: the LLM's self-attention
                                    *     at decode (rotary embedding, in-place key / value cache, split-key attention), see "LLaMA self-attention at
                                    *     decode" below
                                    * 14 (additive): + mmfs_qk_attn_supported / _forward / _backward: the Q-Former's attention with per-head q/k
@@ -875,6 +877,33 @@ int mmfs_llama_attn_decode(int dtype, const void *q_rot, const void *k_cache, co
                            const int32_t *length, const void *bias, int bias_dtype, int64_t bias_stride, int64_t bias_len,
                            void *context, float *workspace, int64_t B, int64_t H, int64_t D, int64_t cap, int64_t kv_bound,
                            void *stream);
+
+/* LLaMA self-attention over a prompt from the same cache (csrc/mmfs_llama_prefill.hip; additive at ABI 14): Lq new tokens a row,
+ * one launch, after mmfs_llama_attn_rope_append has written their slots.  Reads the cache, src_row and length; writes context.
+ *   context [B, Lq, H * 128] of T = softmax_t(q_rot[b, j] . K[src_row[b, t], h, t] / sqrt(128) + bias(b, j, t)) V over the keys
+ *   t < length + Lq (``length``: the tokens held BEFORE the call; the grid comes from (B, H, Lq), the key walk's end from the
+ *   device word).  Slots at or behind length + Lq never enter a product.
+ *   bias  HF's extended mask read where it lies, of ``bias_dtype`` (MMFS_F32 or ``dtype``), or NULL: entry (b, j, t) lies at
+ *       b * bias_batch_stride + j * bias_query_stride + t elements (a stride of 0: one shared batch row / one row for all
+ *       queries); keys at or behind bias_len have none.  Only element-size alignment is assumed.
+ *   flags MMFS_LLAMA_PREFILL_CAUSAL: key t is excluded for query j iff t > length + j (the reference's _make_causal_mask on top
+ *       of the bias); MMFS_LLAMA_PREFILL_VISIT_ALL: no key tile is skipped (the results are the same bits; for tests).
+ *   A key whose bias is at or below finfo(T).min, or which the causal flag excludes, has the score max(bias, finfo(T).min): the
+ *   reference's clamp, which brings HF's finfo.min + finfo.min = -Inf entries of a left-padded prompt back, so a padded query row
+ *   is the finite average of all values (mmfs_llama_attn_decode keeps a -Inf bias as it is).
+ *   No atomics: bit-reproducible, eager or replayed.
+ * mmfs_llama_attn_prefill_tiles: level 0 the query rows of a wave, 1 of a workgroup, 2 the keys of a tile; any other level
+ *   MMFS_E_DIMS.  Host-only.
+ * Errors come back before any launch, as mmfs_llama_attn_decode's; MMFS_E_DIMS also for unknown flag bits, a bias_query_stride
+ * that is neither 0 nor at least bias_len, a bias_batch_stride that is neither 0 nor at least what a batch row's queries span
+ * ((Lq - 1) * bias_query_stride + bias_len).  B * H == 0 returns 0. */
+#define MMFS_LLAMA_PREFILL_CAUSAL 1u
+#define MMFS_LLAMA_PREFILL_VISIT_ALL 2u
+int mmfs_llama_attn_prefill(int dtype, const void *q_rot, const void *k_cache, const void *v_cache, const int32_t *src_row,
+                            const int32_t *length, const void *bias, int bias_dtype, int64_t bias_batch_stride,
+                            int64_t bias_query_stride, int64_t bias_len, unsigned flags, void *context, int64_t B, int64_t Lq,
+                            int64_t H, int64_t D, int64_t cap, void *stream);
+int64_t mmfs_llama_attn_prefill_tiles(int level);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

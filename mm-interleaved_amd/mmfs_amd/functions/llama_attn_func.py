@@ -1,6 +1,7 @@
-"""The LLM's self-attention at decode on the device (csrc/mmfs_llama_attn.hip; C ABI ``mmfs_llama_attn_*`` in
-include/mmfs_msda.h): the rotary embedding and the in-place append to a key / value cache in one launch, and the
-single-token attention over that cache in two (the split walk of the keys, the merge of its partials).  Inference only:
+"""The LLM's self-attention in generation on the device (csrc/mmfs_llama_attn.hip, csrc/mmfs_llama_prefill.hip; C ABI
+``mmfs_llama_attn_*`` in include/mmfs_msda.h): the rotary embedding and the in-place append to a key / value cache in one
+launch, the single-token attention over that cache in two (the split walk of the keys, the merge of its partials), and a
+prompt's attention over it in one (tiled online softmax, the mask read where it lies).  Inference only:
 nothing here is differentiable.  Nothing reads a value back from the device: a step can be captured into a graph.
 
 ``mmfs_amd.llama_attn`` holds the cache (``LlamaKVCache``) and the module (``LlamaSelfAttention``) built on these.
@@ -25,13 +26,22 @@ _lib.mmfs_llama_attn_decode_workspace_bytes.restype = _i64
 _lib.mmfs_llama_attn_decode_workspace_bytes.argtypes = [_i64] * 3
 _lib.mmfs_llama_attn_decode.restype = _int
 _lib.mmfs_llama_attn_decode.argtypes = [_int] + [_vp] * 6 + [_int, _i64, _i64] + [_vp] * 2 + [_i64] * 5 + [_vp]
+if not hasattr(_lib, "mmfs_llama_attn_prefill"):        # (additive at ABI 14 as well)
+    raise ImportError(f"{MSDA.library_path()} has no mmfs_llama_attn_prefill: rebuild the library")
+_lib.mmfs_llama_attn_prefill.restype = _int
+_lib.mmfs_llama_attn_prefill.argtypes = [_int] + [_vp] * 6 + [_int, _i64, _i64, _i64, ctypes.c_uint, _vp] + [_i64] * 5 + [_vp]
+_lib.mmfs_llama_attn_prefill_tiles.restype = _i64
+_lib.mmfs_llama_attn_prefill_tiles.argtypes = [_int]
 _CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
 HEAD_DIM = 128
 # how the decode kernel cuts the keys: a wave's, a workgroup's (= a split's): where its paths change
 WAVE_KEYS, SPLIT_KEYS = int(_lib.mmfs_llama_attn_decode_keys(0)), int(_lib.mmfs_llama_attn_decode_keys(1))
+# how the prefill kernel cuts its work: the query rows of a wave, of a workgroup, the keys of a tile
+PREFILL_TILES = tuple(int(_lib.mmfs_llama_attn_prefill_tiles(i)) for i in range(3))
+PREFILL_CAUSAL, PREFILL_VISIT_ALL = 1, 2                # MMFS_LLAMA_PREFILL_*
 
 # kernel launches since import, for tests and tools that ask which route the module took
-launches = {"append": 0, "decode": 0}
+launches = {"append": 0, "decode": 0, "prefill": 0}
 
 
 def rope_table(head_dim, max_positions, base=10000, device=None):
@@ -156,4 +166,52 @@ def _attn_decode(q_rot, keys, values, length, src_row, bias=None, kv_bound=None)
                           B, H, C // H, cap, kv_bound, MSDA._stream(dev))
     MSDA._check(rc, "mmfs_llama_attn_decode")
     launches["decode"] += 2
+    return out
+
+
+def llama_attn_prefill(q_rot, keys, values, length, src_row, bias=None, causal=False):
+    """q_rot [B, Lq, H 128] (what ``llama_rope_append`` returned; its keys and values are in the cache) -> context
+    [B, Lq, H 128]: softmax over the keys t < length + Lq of q_rot[b, j] . keys[src_row[b, t], h, t] / sqrt(128) +
+    bias[b, j, t], times the values.  ``bias`` [B or 1, 1 or Lq, kv] or HF's 4-d mask [B or 1, 1, 1 or Lq, kv], of fp32 or
+    of the inputs' type, read where it lies through its strides (an expanded view costs nothing).  ``causal``: key t is
+    excluded for query j iff t > length + j, on top of the bias.  A key at or below finfo.min, or excluded, scores
+    finfo.min: rows whose keys are all masked are the mean of the values, also where HF's mask holds -Inf."""
+    _check_cache(q_rot, keys, values, length, src_row, "llama_attn_prefill")
+    B, Lq, _ = q_rot.shape
+    _require(1 <= Lq <= keys.shape[2], "llama_attn_prefill: 1 <= Lq <= the capacity")
+    if bias is not None:
+        _require(isinstance(bias, torch.Tensor) and bias.dim() in (3, 4) and (bias.dim() == 3 or bias.shape[1] == 1)
+                 and bias.shape[0] in (1, B) and bias.shape[-2] in (1, Lq) and bias.shape[-1] <= keys.shape[2],
+                 "llama_attn_prefill: bias must be [B or 1, 1 or Lq, kv] or [B or 1, 1, 1 or Lq, kv], kv within the capacity")
+    return _attn_prefill(q_rot, keys, values, length, src_row, bias, causal)
+
+
+def _attn_prefill(q_rot, keys, values, length, src_row, bias=None, causal=False, visit_all=False):
+    """``llama_attn_prefill`` without its argument checks (see ``_rope_append``); ``visit_all``: no key tile is skipped"""
+    dev, dt = q_rot.device, q_rot.dtype
+    B, Lq, C = q_rot.shape
+    H, cap = keys.shape[1], keys.shape[2]
+    q_rot = _plain(q_rot)
+    bias_t, code, batch_stride, query_stride, blen = None, 0, 0, 0, 0
+    if bias is not None:
+        bias_t = bias.detach()
+        if bias_t.dim() == 4:
+            bias_t = bias_t[:, 0]
+        if bias_t.dtype not in (torch.float32, dt) or bias_t.device != dev:
+            bias_t = bias_t.to(device=dev, dtype=torch.float32)
+        if bias_t.stride(-1) != 1 or bias_t.data_ptr() % bias_t.element_size():
+            bias_t = bias_t.clone(memory_format=torch.contiguous_format)
+        blen = bias_t.shape[-1]
+        batch_stride = 0 if bias_t.shape[0] == 1 else bias_t.stride(0)
+        query_stride = 0 if bias_t.shape[1] == 1 else bias_t.stride(1)
+        code = _CODE[bias_t.dtype]
+    flags = (PREFILL_CAUSAL if causal else 0) | (PREFILL_VISIT_ALL if visit_all else 0)
+    out = torch.empty((B, Lq, C), dtype=dt, device=dev)
+    with MSDA._on_device(dev):
+        rc = MSDA._launch("llama_attn_prefill", dev, _lib.mmfs_llama_attn_prefill, _CODE[dt], q_rot.data_ptr(), keys.data_ptr(),
+                          values.data_ptr(), src_row.data_ptr(), length.data_ptr(),
+                          None if bias_t is None else bias_t.data_ptr(), code, batch_stride, query_stride, blen, flags,
+                          out.data_ptr(), B, Lq, H, C // H, cap, MSDA._stream(dev))
+    MSDA._check(rc, "mmfs_llama_attn_prefill")
+    launches["prefill"] += 1
     return out

@@ -11,8 +11,11 @@
 
 Two routes.  ``"kernels"``: ``past_key_value`` is a handle of a ``LlamaKVCache``; csrc/mmfs_llama_attn.hip rotates q and k,
 appends k and v to the cache where it lies and, for a single new token, walks the keys once (no ``torch.cat``, no
-[B, H, 1, T] tensor); more than one new token (the prefill into the cache) takes the append kernel and then the
-reference's mathematics in framework ops on the rotated q and the cache's views.  Returns the handle as the present.
+[B, H, 1, T] tensor); more than one new token (the prefill into the cache) takes the append kernel and then the prefill
+kernel (csrc/mmfs_llama_prefill.hip: tiled online softmax over the cache, the mask read where it lies, no [B, H, Lq, kv]
+tensor) from ``PREFILL_KERNEL_MIN_TOKENS`` new tokens on, below it the reference's mathematics in framework ops on the
+rotated q and the cache's views; ``module.prefill_kernel = True / False`` forces either, ``module.last_prefill`` says which
+ran.  Returns the handle as the present.
 ``"framework"``: the reference's statement, tuple cache included -- host tensors, fp32, a tuple (or no) cache,
 ``use_cache=False``, ``output_attentions``, autocast, anything that requires grad, a mask that is not
 [B or 1, 1, q_len or 1, kv_len].  The class is a drop-in with or without a ``LlamaKVCache``.  A call that is handed a cache
@@ -27,6 +30,9 @@ from torch import nn
 # which route device tensors with a cache handle take when nothing is forced, per shape class (profiles/llama_attn.md
 # holds the measurement behind it)
 DEFAULT_ROUTE = {"decode": "kernels", "prefill": "kernels"}
+# on the kernel route, a prompt of at least this many new tokens takes the prefill kernel behind the append, a shorter one
+# the framework ops on the cache's views (2: always; profiles/llama_attn.md holds the measurement behind it)
+PREFILL_KERNEL_MIN_TOKENS = 2
 
 
 def _func():
@@ -194,6 +200,8 @@ class LlamaSelfAttention(nn.Module):
         self.route = None                       # None: DEFAULT_ROUTE where the kernels apply
         self.last_route = None                  # what the last forward took (tests, tools)
         self.last_reason = None                 # why it was the framework route
+        self.prefill_kernel = None              # None: PREFILL_KERNEL_MIN_TOKENS decides; True / False: the prefill kernel / framework ops
+        self.last_prefill = None                # "kernel" / "framework ops": what the last prompt on the kernel route took
 
     def rope(self, device, positions=0):
         """(cos, sin) [>= positions, head_dim / 2] fp32 on ``device``; grown when a sequence is longer, as the reference's"""
@@ -246,6 +254,8 @@ class LlamaSelfAttention(nn.Module):
         forced = self.route is not None
         if forced and self.route not in ("kernels", "framework"):
             raise ValueError(f"route: {self.route!r} is not 'kernels' or 'framework'")
+        if not (self.prefill_kernel is None or isinstance(self.prefill_kernel, bool)):
+            raise ValueError(f"prefill_kernel: {self.prefill_kernel!r} is not None, True or False")
         rows, q_len = hidden_states.shape[0], hidden_states.shape[1]
         q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
         reason = self._kernel_reason(hidden_states, q, attention_mask, past_key_value, output_attentions, use_cache)
@@ -280,8 +290,13 @@ class LlamaSelfAttention(nn.Module):
             # at later lengths), the mirror otherwise; the result does not depend on it
             bound = cache.cap if capturing else cache.host_length + 1
             context = f._attn_decode(q_rot, layer.keys, layer.values, cache.length, cache.src_row, bias, bound)
+        elif q_len >= PREFILL_KERNEL_MIN_TOKENS if self.prefill_kernel is None else self.prefill_kernel:
+            # the mask as it lies: [B or 1, 1, q_len or 1, kv_len], its strides read from the tensor
+            context = f._attn_prefill(q_rot, layer.keys, layer.values, cache.length, cache.src_row, mask)
+            self.last_prefill = "kernel"
         else:
             context = self._attend(self._split(q_rot), layer[0], layer[1], mask, False)[0]
+            self.last_prefill = "framework ops"
         return self.o_proj(context), None, layer
 
     # ------------------------------------------------------------------------------------------ the framework route

@@ -15,9 +15,13 @@ process, the median of 5 rounds with their spread; per layer-step = step / layer
 layer's keys and values, 2 B H T D e; their rate is set against the 6.3 TB/s a streaming kernel reaches on an MI355X.
 ``graph`` columns: the same step of either route captured once with ``torch.cuda.graph`` and replayed -- the device's
 share of the time, without the host's gaps between launches.
-``prefill`` lines: a prompt of Lq = 128, 512 and 2048 tokens into an empty cache, B = 4, causal mask -- the framework route's
-rope and attention on the new keys as they lie, against the kernel route's: ``llama_rope_append`` and then the same
-attention in framework ops on the cache's views (strided in the key axis: the capacity is Lq + 64).
+``prefill`` lines: a prompt of Lq = 2, 16, 128, 512 and 2048 tokens into an empty cache and one chunk of 512 onto 1536 held
+tokens, B = 4, HF's mask as the reference builds it (left padding of 0 .. 3 + causal, in bf16) -- the framework route's
+rope and attention on the new keys as they lie, against the kernel route's two forms, alternating in one process:
+``llama_rope_append`` and then the same attention in framework ops on the cache's views (strided in the key axis: the
+capacity is 64 more than the keys; what ``prefill_kernel = False`` selects), and ``llama_rope_append`` and then the prefill
+kernel (csrc/mmfs_llama_prefill.hip), once on that mask as it lies and once on the padding row with the causal flag.
+Algorithmic FLOPs are 4 B H D (Lq held + Lq (Lq + 1) / 2): the causal half of the two products, over the median time.
 Prints one JSON line; ``--md PATH`` also writes the tables.
     python tools/llama_attn_bench.py [--md profiles/llama_attn_table.md]
 Not the contract benchmark (bench.py)."""
@@ -36,7 +40,8 @@ import torch  # noqa: E402
 import mmfs_amd  # noqa: E402
 from mmfs_amd.llama_attn import LlamaKVCache, LlamaSelfAttention  # noqa: E402
 # the entries LlamaSelfAttention calls (the public llama_rope_append / llama_attn_decode check their arguments on the host first)
-from mmfs_amd.functions.llama_attn_func import _attn_decode as attn_decode, _rope_append as rope_append  # noqa: E402
+from mmfs_amd.functions.llama_attn_func import (_attn_decode as attn_decode, _attn_prefill as attn_prefill,  # noqa: E402
+                                                _rope_append as rope_append)
 
 dev = torch.device("cuda:0")
 DT = torch.bfloat16
@@ -84,12 +89,13 @@ def graphed(fn):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--md")
+    ap.add_argument("--only", choices=("decode", "prefill"), help="one half of the lines (the table then has that half alone)")
     args = ap.parse_args()
     cfg = types.SimpleNamespace(hidden_size=H * D, num_attention_heads=H, max_position_embeddings=2048)
     m = LlamaSelfAttention(cfg)                        # (its four Linear layers stay on the host: they are not timed)
     cos, sin = m.rope(dev)
     rows = []
-    for B, T in SHAPES:
+    for B, T in () if args.only == "prefill" else SHAPES:
         beams = B > 4
         layer_bytes = 2 * B * H * T * D * 2
         layers = max(2, min(32, math.ceil(2 ** 30 / layer_bytes)))
@@ -151,14 +157,22 @@ def main():
         del cache, past, last
         torch.cuda.empty_cache()
     prefill = []
-    for Lq in (128, 512, 2048):
-        B = 4
+    for held, Lq in () if args.only == "decode" else ((0, 2), (0, 16), (0, 128), (0, 512), (0, 2048), (1536, 512)):
+        B, n = 4, held + Lq
         gen = torch.Generator(device=dev).manual_seed(1)
         draw = lambda *s: torch.empty(s, dtype=DT, device=dev).normal_(0.0, 1.0, generator=gen)
         q, k, v = draw(B, Lq, H * D), draw(B, Lq, H * D), draw(B, Lq, H * D)
-        pos = torch.arange(Lq, device=dev)[None].expand(B, -1).contiguous()
-        mask = torch.full((Lq, Lq), torch.finfo(DT).min, dtype=DT, device=dev).triu(1)[None, None].expand(B, 1, Lq, Lq)
-        cache = LlamaKVCache(1, B, H, Lq + 64, D, DT, dev)
+        pos = torch.arange(held, n, device=dev)[None].expand(B, -1).contiguous()
+        # HF's mask as the reference builds it: _expand_mask (left padding of 0 .. 3) + _make_causal_mask, in T
+        low = torch.finfo(DT).min
+        keep = torch.arange(n, device=dev)[None, :] >= torch.arange(B, device=dev)[:, None] % 4
+        row = torch.where(keep, 0.0, low).to(DT)[:, None, None, :]                                   # [B, 1, 1, n]
+        causal = torch.cat((torch.zeros(Lq, held, dtype=DT, device=dev), torch.full((Lq, Lq), low, dtype=DT, device=dev).triu(1)), -1)
+        mask = row.expand(B, 1, Lq, n) + causal[None, None]
+        cache = LlamaKVCache(1, B, H, n + 64, D, DT, dev)
+        cache.store[:, :, :, :, :held].normal_(0.0, 1.0, generator=gen)
+        cache.set_length(held)
+        past = (cache.store[0, 0, :, :, :held].clone(), cache.store[0, 1, :, :, :held].clone())
         last = {}
 
         def framework():
@@ -168,27 +182,51 @@ def main():
                 hq, hk, hv = m._split(q), m._split(k), m._split(v)
                 hq = hq * c + mmfs_amd.llama_attn.rotate_half(hq) * s
                 hk = hk * c + mmfs_amd.llama_attn.rotate_half(hk) * s
+                if held:
+                    hk, hv = torch.cat((past[0], hk), dim=2), torch.cat((past[1], hv), dim=2)
                 last["framework"] = m._attend(hq, hk, hv, mask, False)[0]
 
-        def kernels():
-            with torch.no_grad():
-                layer = cache[0]
-                q_rot = rope_append(q, k, v, pos, cos, sin, layer.keys, layer.values, cache.length, cache.src_row)
-                last["kernels"] = m._attend(m._split(q_rot), layer.keys[:, :, :Lq], layer.values[:, :, :Lq], mask, False)[0]
+        def append():
+            layer = cache[0]
+            return layer, rope_append(q, k, v, pos, cos, sin, layer.keys, layer.values, cache.length, cache.src_row)
 
-        framework()
-        kernels()
+        def kernels():                                 # append + framework ops on the cache's views (prefill_kernel = False)
+            with torch.no_grad():
+                layer, q_rot = append()
+                last["kernels"] = m._attend(m._split(q_rot), layer.keys[:, :, :n], layer.values[:, :, :n], mask, False)[0]
+
+        def prefill_hf():                              # append + the prefill kernel on HF's mask as it lies
+            layer, q_rot = append()
+            last["prefill_hf"] = attn_prefill(q_rot, layer.keys, layer.values, cache.length, cache.src_row, mask)
+
+        def prefill_flag():                            # append + the prefill kernel: the padding row and the causal flag
+            layer, q_rot = append()
+            last["prefill_flag"] = attn_prefill(q_rot, layer.keys, layer.values, cache.length, cache.src_row, row, True)
+
+        fns = {"framework": framework, "kernels": kernels, "prefill_hf": prefill_hf, "prefill_flag": prefill_flag}
+        for f in fns.values():
+            f()
         torch.cuda.synchronize()
-        gap = float((last["framework"].double() - last["kernels"].double()).abs().max())
-        t = interleaved({"framework": framework, "kernels": kernels})
-        prefill.append(dict(B=B, Lq=Lq, framework_us=round(t["framework"][0] * 1e3, 1), kernels_us=round(t["kernels"][0] * 1e3, 1),
-                            framework_spread_us=round(t["framework"][1] * 1e3, 1), kernels_spread_us=round(t["kernels"][1] * 1e3, 1),
-                            agree_max_abs=gap))
-        del cache, last
+        gap = {name: float((last["framework"].double() - last[name].double()).abs().max()) for name in fns if name != "framework"}
+        scale = float(last["framework"].double().abs().max())
+        last.clear()
+        t = interleaved(fns)
+        flops = 4 * B * H * D * (Lq * held + Lq * (Lq + 1) // 2)
+        r = dict(B=B, held=held, Lq=Lq, context_scale=scale, algorithmic_GFLOP=round(flops / 1e9, 2))
+        for name in fns:
+            r[name + "_us"], r[name + "_spread_us"] = round(t[name][0] * 1e3, 1), round(t[name][1] * 1e3, 1)
+            if name != "framework":
+                r[name + "_max_abs_to_framework"] = gap[name]
+        for name in ("prefill_hf", "prefill_flag"):
+            r[name + "_algorithmic_TFLOPs"] = round(flops / (t[name][0] * 1e-3) / 1e12, 1)
+            # the kernel is the default on a line only where its median gain over append + framework ops exceeds both spreads
+            r[name + "_gain_exceeds_spreads"] = t["kernels"][0] - t[name][0] > max(t["kernels"][1], t[name][1])
+        prefill.append(r)
+        del cache, last, past, mask
         torch.cuda.empty_cache()
     print(json.dumps({"decode": rows, "prefill": prefill}))
     if args.md:
-        lines = ["| B | T | beams | layers walked | framework us | kernels us | speed-up | algorithmic MB | kernels: share of 6.3 TB/s "
+        lines = [] if args.only == "prefill" else ["| B | T | beams | layers walked | framework us | kernels us | speed-up | algorithmic MB | kernels: share of 6.3 TB/s "
                  "| framework: share | graph: framework us | graph: kernels us | graph: kernels' share | max abs difference "
                  "(context scale) |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
         for r in rows:
@@ -197,10 +235,18 @@ def main():
                          f"{r['algorithmic_MB']} | {r['kernels_share_of_stream']} | {r['framework_share_of_stream']} | "
                          f"{r['framework_graph_us']} | {r['kernels_graph_us']} | {r['kernels_graph_share_of_stream']} | "
                          f"{r['agree_max_abs']:.3g} ({r['context_scale']:.3g}) |")
-        lines += ["", "| B | prompt Lq | framework us | kernels us | max abs difference |", "|---|---|---|---|---|"]
+        lines += [] if args.only == "decode" else ["", "| B | held | prompt Lq | framework us | append + framework ops us | append + prefill kernel, HF mask us | "
+                  "append + prefill kernel, padding row + causal flag us | algorithmic GFLOP | algorithmic TFLOP/s (HF mask / flag) | "
+                  "gain over append + framework ops exceeds both spreads (HF mask / flag) | max abs difference to framework "
+                  "(ops / HF mask / flag; context scale) |", "|---|---|---|---|---|---|---|---|---|---|---|"]
         for r in prefill:
-            lines.append(f"| {r['B']} | {r['Lq']} | {r['framework_us']} +- {r['framework_spread_us']} | {r['kernels_us']} +- "
-                         f"{r['kernels_spread_us']} | {r['agree_max_abs']:.3g} |")
+            pm = lambda name: f"{r[name + '_us']} +- {r[name + '_spread_us']}"
+            lines.append(f"| {r['B']} | {r['held']} | {r['Lq']} | {pm('framework')} | {pm('kernels')} | {pm('prefill_hf')} | "
+                         f"{pm('prefill_flag')} | {r['algorithmic_GFLOP']} | {r['prefill_hf_algorithmic_TFLOPs']} / "
+                         f"{r['prefill_flag_algorithmic_TFLOPs']} | {'yes' if r['prefill_hf_gain_exceeds_spreads'] else 'no'} / "
+                         f"{'yes' if r['prefill_flag_gain_exceeds_spreads'] else 'no'} | {r['kernels_max_abs_to_framework']:.3g} / "
+                         f"{r['prefill_hf_max_abs_to_framework']:.3g} / {r['prefill_flag_max_abs_to_framework']:.3g} "
+                         f"({r['context_scale']:.3g}) |")
         with open(args.md, "w") as f:
             f.write("\n".join(lines) + "\n")
 
