@@ -86,18 +86,14 @@
 //   Measured worst ratios |got - ref| / bound are kept in profiles/qk_attn.md.
 //
 // Offsets are 64-bit.
-#include "msda_host.h"
-#include "msda_mma_common.h"
+#include "mmfs_attn_core.h"
 #include <hip/hip_runtime.h>
-#include <math.h>
 
 namespace mmfs {
 
 namespace {
 
-using mma::f32x4;
-using mma::s16x4;
-using mma::s16x8;
+using namespace attn;
 
 constexpr int kD = 64;
 constexpr int kThreads = 256;
@@ -108,23 +104,7 @@ constexpr int kKT = 64;                 // keys of a tile
 constexpr int kLd = 72;                 // elements between rows of a row-major image [row][64 channels + 8]: 144 bytes
 constexpr int kLdKt = 72;               // transposed key tile [channel][64 keys + 8]
 constexpr int kLdQt = 136;              // transposed query-side image [channel][128 queries + 8]
-constexpr float kScale = 0.125f;        // 1 / sqrt(64)
-constexpr float kLog2e = 1.44269504088896340736f;
-
-__device__ __forceinline__ float exp_hw(float d) { return __builtin_amdgcn_exp2f(d * kLog2e); }
-
-// finfo(T).min: a key whose bias is at or below it is a MASKED key and its score is the bias itself -- what the framework's
-// sum in T leaves of score + finfo(T).min (bf16: fp32 absorbs the score as well; fp16: -65504 + score would not).
-// Where the two part: in fp16 the framework's sum is -65504 only while |score / 8| < 16 (half a unit of 65504); at
-// score / 8 <= -16 it rounds to -Inf (the key is excluded; a row of such keys is NaN) and at >= 16 to -65472, while here the
-// key stays at -65504.  Out of reach with qk-norm at any sane scale (|q^ . k^| / 8 of a few units), reachable without it.
-template <typename T> struct Lowest;
-template <> struct Lowest<bf16_t> { static constexpr float value = -3.3895313892515355e38f; };
-template <> struct Lowest<half_t> { static constexpr float value = -65504.f; };
-template <typename T> __device__ __forceinline__ float score_of(float dot, float bias)
-{
-    return bias <= Lowest<T>::value ? bias : dot * kScale + bias;
-}
+constexpr float kScale = HeadScale<kD>::value;
 
 // a small vector of fp32 or of T read by index (the LayerNorm parameters, the key bias); ``f32`` is uniform
 template <typename T> struct Small {
@@ -175,31 +155,6 @@ __device__ __forceinline__ void stage_rows(const T *__restrict__ src, int64_t ld
             for (int e = 0; e < 8; ++e) trans[(c0 + e) * tld + r] = hw[e];
         }
     }
-}
-
-__device__ __forceinline__ s16x8 lds8(const uint16_t *p) { return *reinterpret_cast<const s16x8 *>(p); }
-
-// elements 0..3 at p, 4..7 at p + 16: the k order of an accumulator pair used as the other operand
-__device__ __forceinline__ s16x8 lds4x2(const uint16_t *p)
-{
-    const s16x4 a = *reinterpret_cast<const s16x4 *>(p), b = *reinterpret_cast<const s16x4 *>(p + 16);
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// registers 0..3 of two accumulators, rounded to T: k-slots 0..3 and 4..7 of the lane's fragment
-template <typename T> __device__ __forceinline__ s16x8 pack_pair(const float (&a)[4], const float (&b)[4])
-{
-    const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    const uint4 w = Vec16<T>::pack(v);
-    return __builtin_bit_cast(s16x8, w);
-}
-
-template <typename T> __device__ __forceinline__ void store4(T *p, const float (&v)[4])
-{
-    uint2 w;
-    w.x = Vec16<T>::pk(v[0], v[1]);
-    w.y = Vec16<T>::pk(v[2], v[3]);
-    *reinterpret_cast<uint2 *>(p) = w;
 }
 
 template <typename T> __device__ __forceinline__ void load4(const T *p, float (&v)[4])
@@ -266,8 +221,8 @@ qk_attn_fwd(const T *__restrict__ q, const T *__restrict__ k, const T *__restric
                 for (int st = 0; st < 2; ++st)
                     a = mma::FwdMma<T>::run(lds8(sK + (kb16 * 16 + c) * kLd + 32 * st + 8 * g), fq[i][st], a);
                 const float4 bs = *reinterpret_cast<const float4 *>(sBias + kb16 * 16 + 4 * g);
-                s[kb16][0] = score_of<T>(a[0], bs.x); s[kb16][1] = score_of<T>(a[1], bs.y);
-                s[kb16][2] = score_of<T>(a[2], bs.z); s[kb16][3] = score_of<T>(a[3], bs.w);
+                s[kb16][0] = score_of<T, kD>(a[0], bs.x); s[kb16][1] = score_of<T, kD>(a[1], bs.y);
+                s[kb16][2] = score_of<T, kD>(a[2], bs.z); s[kb16][3] = score_of<T, kD>(a[3], bs.w);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tm = fmaxf(tm, s[kb16][r]);
             }
@@ -406,7 +361,7 @@ qk_attn_bwd(const T *__restrict__ q, const T *__restrict__ k, const T *__restric
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int qi = q0 + 4 * g + r;
-                    const float x = score_of<T>(s[r], bias_c);
+                    const float x = score_of<T, kD>(s[r], bias_c);
                     const float pr = key_ok && qi < Nq ? exp_hw(x - sM[qi]) * sRl[qi] : 0.f;
                     p[hf][r] = pr;
                     ds[hf][r] = key_ok && qi < Nq ? pr * (dp[r] - sDelta[qi]) : 0.f;
@@ -568,17 +523,12 @@ int check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Nq, int64_t Nk)
     return MMFS_OK;
 }
 
-// the type of a small fp32-or-T vector: 1 fp32, 0 T, < 0 neither
-int small_f32(int small_dtype, int dtype) { return small_dtype == MMFS_F32 ? 1 : small_dtype == dtype ? 0 : -1; }
-
 // the four LayerNorm pointers: all or none
 int norm_of(const void *a, const void *b, const void *c, const void *d)
 {
     const int n = (a != nullptr) + (b != nullptr) + (c != nullptr) + (d != nullptr);
     return n == 4 ? 1 : n == 0 ? 0 : -1;
 }
-
-template <typename F> int by_half_type(int dtype, F &&f) { return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t()); }
 
 }  // namespace
 }  // namespace mmfs
@@ -607,8 +557,8 @@ int qk_attn_check(int dtype, const void *q, const void *k, const void *v, const 
     if (key_bias && bias_stride != 0 && bias_stride != Nk) return MMFS_E_DIMS;
     if (B * H && (!q || !k || !v)) return MMFS_E_NULLPTR;
     const uintptr_t small = (uintptr_t)qw | (uintptr_t)qb | (uintptr_t)kw | (uintptr_t)kb;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || small % (a.norm_f32 ? 4 : 2) ||
-        (uintptr_t)key_bias % (a.bias_f32 ? 4 : 2))
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || !small_aligned(small, a.norm_f32) ||
+        !small_aligned((uintptr_t)key_bias, a.bias_f32))
         return MMFS_E_ALIGN;
     return MMFS_OK;
 }

@@ -34,14 +34,11 @@
 // be captured, and every sum has a fixed order that depends on n alone (not on the grid): results are bit-reproducible,
 // eager or replayed.
 //
-// Masked keys, the rule of mmfs_attn.hip: ``bias`` ([B, kv_len] or one shared row, fp32 or T, read where it lies) is HF's
-// extended mask without its broadcast axes; a bias at or below finfo(T).min IS the key's score -- what the reference's
-// ``+ mask`` followed by ``max(., finfo.min)`` leaves in T.  Keys that are all masked give the uniform average of v, as
-// the reference does; a row of -Inf biases gives NaN, as softmax(-Inf ..) does.  Where fp16 parts from this: the
-// framework's sum -65504 + s is -65504 while |s| < 16; at s <= -16 it rounds to -Inf and the reference's max(., finfo.min)
-// brings it BACK to -65504 (unlike the Q-Former's statement, which has no such clamp), so only s >= 16 parts: the
-// framework then has -65472 (or above) where this kernel keeps -65504 -- a masked key 32 units above its masked
-// neighbours, visible only in a row whose keys are all masked.  In bf16 finfo.min absorbs every fp32 score.
+// Masked keys, the rule of mmfs_attn_core.h's score_of: ``bias`` ([B, kv_len] or one shared row, fp32 or T, read where it
+// lies) is HF's extended mask without its broadcast axes; a bias at or below finfo(T).min IS the key's score -- what the
+// reference's ``+ mask`` followed by ``max(., finfo.min)`` leaves in T.  Keys that are all masked give the uniform average
+// of v, as the reference does; a row of -Inf biases gives NaN, as softmax(-Inf ..) does.  Where fp16 parts from this
+// (a masked key whose product is at or above 16) is said there.  In bf16 finfo.min absorbs every fp32 score.
 //
 // Resources (make asm, gfx950; no spills, no scratch):
 //                               VGPRs  AGPRs  LDS bytes  waves / SIMD
@@ -83,15 +80,16 @@
 //   Measured worst ratios |got - ref| / bound are kept in profiles/llama_attn.md.
 //
 // Offsets are 64-bit.
-#include "msda_host.h"
+#include "mmfs_attn_core.h"
 #include <hip/hip_runtime.h>
-#include <math.h>
 
 namespace mmfs {
 
 namespace {
 
-constexpr int kD = 128;                 // channels of a head
+using namespace attn;
+
+constexpr int kD = kLlamaD;             // channels of a head
 constexpr int kHalf = 64;               // a channel's rotary partner is kHalf further on
 constexpr int kThreads = 256;          // llama_rope_append
 constexpr int kWaves = 8;               // llama_attn_decode: waves of a workgroup
@@ -101,20 +99,6 @@ constexpr int kLoads = kWaveKeys / 4;
 constexpr int kSplitKeys = kWaves * kWaveKeys;      // keys of a workgroup = of a split: 256
 constexpr int kPartial = 4 + kD;        // floats of a partial: m, l, two unused, o[128] (16-byte rows)
 constexpr int kMergeThreads = 128;      // 8 (b, h) pairs of 16 lanes
-constexpr int64_t kMaxCap = 1 << 22;    // splits <= 16384 (grid.y)
-constexpr float kScale = 0.08838834764831845f;      // 1 / sqrt(128)
-constexpr float kLog2e = 1.44269504088896340736f;
-
-__device__ __forceinline__ float exp_hw(float d) { return __builtin_amdgcn_exp2f(d * kLog2e); }
-
-template <typename T> struct Lowest;
-template <> struct Lowest<bf16_t> { static constexpr float value = -3.3895313892515355e38f; };
-template <> struct Lowest<half_t> { static constexpr float value = -65504.f; };
-// a bias at or below finfo(T).min marks a masked key: its score is the bias itself (the header says where fp16 parts)
-template <typename T> __device__ __forceinline__ float score_of(float dot, float bias)
-{
-    return bias <= Lowest<T>::value ? bias : dot * kScale + bias;
-}
 
 __device__ __forceinline__ void load8f(const float *p, float (&o)[8])
 {
@@ -235,7 +219,7 @@ llama_attn_decode(const T *__restrict__ q_rot, const T *__restrict__ kc, const T
             for (int e = 0; e < 8; ++e) d += qf[e] * kf[e];
             d = group_add<16>(d);
             const float bs = __shfl(bias_l, 4 * i + g, 64);
-            s[i] = w0 + 4 * i + g < n ? score_of<T>(d, bs) : -INFINITY;
+            s[i] = w0 + 4 * i + g < n ? score_of<T, kD>(d, bs) : -INFINITY;
             m = fmaxf(m, s[i]);
         }
         m = fmaxf(m, __shfl_xor(m, 16, 64));
@@ -315,30 +299,17 @@ llama_attn_merge(const float *__restrict__ partials, const int32_t *__restrict__
     store_vec<T, 8, false>(ctx + (int64_t)bh * kD + c * 8, O);
 }
 
-bool supported(int dtype, int64_t D, int64_t Lq, int64_t cap)
-{
-    return (dtype == MMFS_F16 || dtype == MMFS_BF16) && D == kD && cap >= 1 && cap <= kMaxCap && Lq >= 1 && Lq <= cap;
-}
-
-int check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lq, int64_t cap)
-{
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
-    if (B < 0 || H < 0 || D < 0 || Lq < 0 || cap < 0) return MMFS_E_DIMS;
-    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
-    if (!supported(dtype, D, Lq, cap)) return MMFS_E_UNSUPPORTED;
-    return MMFS_OK;
-}
-
 int64_t splits_of(int64_t kv_bound) { return (kv_bound + kSplitKeys - 1) / kSplitKeys; }
-
-template <typename F> int by_half_type(int dtype, F &&f) { return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t()); }
 
 }  // namespace
 }  // namespace mmfs
 
 extern "C" {
 
-int mmfs_llama_attn_supported(int dtype, int64_t D, int64_t Lq, int64_t cap) { return mmfs::supported(dtype, D, Lq, cap); }
+int mmfs_llama_attn_supported(int dtype, int64_t D, int64_t Lq, int64_t cap)
+{
+    return mmfs::attn::llama_supported(dtype, D, Lq, cap);
+}
 
 int mmfs_llama_attn_rope_append(int dtype, const void *q, const void *k, const void *v, const int64_t *position_ids,
                                 const float *cos_table, const float *sin_table, int64_t max_pos, const int32_t *length,
@@ -346,7 +317,7 @@ int mmfs_llama_attn_rope_append(int dtype, const void *q, const void *k, const v
                                 int64_t D, int64_t cap, void *stream)
 {
     using namespace mmfs;
-    const int rc = check(dtype, B, H, D, Lq, cap);
+    const int rc = llama_check(dtype, B, H, D, Lq, cap);
     if (rc) return rc;
     if (max_pos < 0 || max_pos > (1LL << 40) || B * Lq > (1LL << 32) || B * Lq * H > (1LL << 34)) return MMFS_E_DIMS;
     if (B * H == 0) return MMFS_OK;
@@ -374,7 +345,7 @@ int64_t mmfs_llama_attn_decode_keys(int level)
 int64_t mmfs_llama_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_t kv_bound)
 {
     using namespace mmfs;
-    if (B < 0 || H < 0 || kv_bound < 1 || kv_bound > kMaxCap || B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24))
+    if (B < 0 || H < 0 || kv_bound < 1 || kv_bound > kLlamaMaxCap || B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24))
         return MMFS_E_DIMS;
     return B * H * splits_of(kv_bound) * kPartial * (int64_t)sizeof(float);
 }
@@ -385,17 +356,17 @@ int mmfs_llama_attn_decode(int dtype, const void *q_rot, const void *k_cache, co
                            void *stream)
 {
     using namespace mmfs;
-    const int rc = check(dtype, B, H, D, 1, cap);
+    int rc = llama_check(dtype, B, H, D, 1, cap);
     if (rc) return rc;
     if (kv_bound < 1 || kv_bound > cap) return MMFS_E_DIMS;
-    const int bias_f32 = !bias || bias_dtype == MMFS_F32 ? 1 : bias_dtype == dtype ? 0 : -1;
-    if (bias_f32 < 0) return MMFS_E_DTYPE;
-    if (bias && (bias_len < 0 || bias_len > kMaxCap || (bias_stride != 0 && bias_stride < bias_len) || bias_stride > kMaxCap))
-        return MMFS_E_DIMS;
+    int bias_f32;
+    rc = llama_bias(bias, bias_dtype, dtype, bias_len, bias_f32);
+    if (rc) return rc;
+    if (bias && ((bias_stride != 0 && bias_stride < bias_len) || bias_stride > kLlamaMaxCap)) return MMFS_E_DIMS;
     if (B * H == 0) return MMFS_OK;
     if (!q_rot || !k_cache || !v_cache || !src_row || !length || !context || !workspace) return MMFS_E_NULLPTR;
     if (((uintptr_t)q_rot | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)context | (uintptr_t)workspace) % 16 ||
-        ((uintptr_t)src_row | (uintptr_t)length) % 4 || (uintptr_t)bias % (bias_f32 ? 4 : 2))
+        ((uintptr_t)src_row | (uintptr_t)length) % 4 || !small_aligned((uintptr_t)bias, bias_f32))
         return MMFS_E_ALIGN;
     const int64_t splits = splits_of(kv_bound);
     return by_half_type(dtype, [&](auto tag) {

@@ -20,7 +20,7 @@
 // finfo.min + finfo.min = -Inf at the pad-key x future-key entries of a left-padded row: a padded query row is the FINITE
 // uniform average of all n value rows, not NaN.  (The decode kernel keeps a -Inf bias as the score: a row of them is NaN
 // there, as softmax(-Inf ..) is.  A single token's mask is a padding row alone and never holds such a sum.)  In fp16 the
-// framework's -65504 + s parts from this at s >= 16 exactly as mmfs_llama_attn.hip's header says.
+// framework's -65504 + s parts from this at s >= 16 exactly as score_of's comment in mmfs_attn_core.h says.
 // Slots at or behind n are never live: their K and V rows are REPLACED by zeros as a tile is staged (their score is -Inf,
 // p = 0) -- a NaN there reaches no product.  A src_row entry outside [0, B) is never dereferenced: that key's K and V are
 // NaN, so the error shows.  Query rows at or behind Lq in the last tile repeat row Lq - 1 and are not stored.
@@ -70,20 +70,16 @@
 // with one rescaling a tile: at most n / 64 + 1 further roundings a row on top of the n additions, inside c_e = 256 + n.
 //
 // Offsets are 64-bit.
-#include "msda_host.h"
-#include "msda_mma_common.h"
+#include "mmfs_attn_core.h"
 #include <hip/hip_runtime.h>
-#include <math.h>
 
 namespace mmfs {
 
 namespace {
 
-using mma::f32x4;
-using mma::s16x4;
-using mma::s16x8;
+using namespace attn;
 
-constexpr int kD = 128;
+constexpr int kD = kLlamaD;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kWaveRows = 32;           // query rows of a wave: two blocks of 16
@@ -92,42 +88,9 @@ constexpr int kKT = 64;                 // keys of a tile
 constexpr int kLdK = kD + 8;            // elements between rows of the key tile [key][128 + 8]
 constexpr int kLdV = kKT + 4;           // of the transposed value tile [channel][64 + 4]
 constexpr int kLdB = kKT + 4;           // floats between rows of the bias tile
-constexpr int64_t kMaxCap = 1 << 22;
-constexpr float kScale = 0.08838834764831845f;      // 1 / sqrt(128)
-constexpr float kLog2e = 1.44269504088896340736f;
+constexpr float kScale = HeadScale<kD>::value;
 constexpr float kSkipMargin = 1024.f;   // m - finfo.min at or above it: exp2((finfo.min - m) log2 e) is exactly 0
 constexpr unsigned kCausal = MMFS_LLAMA_PREFILL_CAUSAL, kVisitAll = MMFS_LLAMA_PREFILL_VISIT_ALL;
-
-__device__ __forceinline__ float exp_hw(float d) { return __builtin_amdgcn_exp2f(d * kLog2e); }
-
-template <typename T> struct Lowest;
-template <> struct Lowest<bf16_t> { static constexpr float value = -3.3895313892515355e38f; static constexpr uint32_t nan2 = 0x7fc07fc0u; };
-template <> struct Lowest<half_t> { static constexpr float value = -65504.f; static constexpr uint32_t nan2 = 0x7e007e00u; };
-
-__device__ __forceinline__ s16x8 lds8(const uint16_t *p) { return *reinterpret_cast<const s16x8 *>(p); }
-
-// elements 0..3 at p, 4..7 at p + 16: the k order of an accumulator pair used as the other operand
-__device__ __forceinline__ s16x8 lds4x2(const uint16_t *p)
-{
-    const s16x4 a = *reinterpret_cast<const s16x4 *>(p), b = *reinterpret_cast<const s16x4 *>(p + 16);
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// registers 0..3 of two accumulators, rounded to T: k-slots 0..3 and 4..7 of the lane's fragment
-template <typename T> __device__ __forceinline__ s16x8 pack_pair(const float (&a)[4], const float (&b)[4])
-{
-    const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    const uint4 w = Vec16<T>::pack(v);
-    return __builtin_bit_cast(s16x8, w);
-}
-
-template <typename T> __device__ __forceinline__ void store4(T *p, const float (&v)[4])
-{
-    uint2 w;
-    w.x = Vec16<T>::pk(v[0], v[1]);
-    w.y = Vec16<T>::pk(v[2], v[3]);
-    *reinterpret_cast<uint2 *>(p) = w;
-}
 
 __device__ __forceinline__ float wave_max(float v)
 {
@@ -398,22 +361,6 @@ llama_attn_prefill(const T *__restrict__ q_rot, const T *__restrict__ kc, const 
     }
 }
 
-bool supported(int dtype, int64_t D, int64_t Lq, int64_t cap)
-{
-    return (dtype == MMFS_F16 || dtype == MMFS_BF16) && D == kD && cap >= 1 && cap <= kMaxCap && Lq >= 1 && Lq <= cap;
-}
-
-int check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lq, int64_t cap)
-{
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
-    if (B < 0 || H < 0 || D < 0 || Lq < 0 || cap < 0) return MMFS_E_DIMS;
-    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
-    if (!supported(dtype, D, Lq, cap)) return MMFS_E_UNSUPPORTED;
-    return MMFS_OK;
-}
-
-template <typename F> int by_half_type(int dtype, F &&f) { return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t()); }
-
 }  // namespace
 }  // namespace mmfs
 
@@ -430,14 +377,14 @@ int mmfs_llama_attn_prefill(int dtype, const void *q_rot, const void *k_cache, c
                             int64_t H, int64_t D, int64_t cap, void *stream)
 {
     using namespace mmfs;
-    const int rc = check(dtype, B, H, D, Lq, cap);
+    int rc = llama_check(dtype, B, H, D, Lq, cap);
     if (rc) return rc;
     if (flags & ~(kCausal | kVisitAll)) return MMFS_E_DIMS;
-    const int bias_f32 = !bias || bias_dtype == MMFS_F32 ? 1 : bias_dtype == dtype ? 0 : -1;
-    if (bias_f32 < 0) return MMFS_E_DTYPE;
+    int bias_f32;
+    rc = llama_bias(bias, bias_dtype, dtype, bias_len, bias_f32);
+    if (rc) return rc;
     if (bias) {
         constexpr int64_t kMaxStride = (int64_t)1 << 40;
-        if (bias_len < 0 || bias_len > kMaxCap) return MMFS_E_DIMS;
         if (bias_query_stride != 0 && (bias_query_stride < bias_len || bias_query_stride > kMaxStride)) return MMFS_E_DIMS;
         // what the queries of one batch row span
         const int64_t extent = bias_query_stride ? (Lq - 1) * bias_query_stride + bias_len : bias_len;
@@ -448,7 +395,7 @@ int mmfs_llama_attn_prefill(int dtype, const void *q_rot, const void *k_cache, c
     if (B * H == 0) return MMFS_OK;
     if (!q_rot || !k_cache || !v_cache || !src_row || !length || !context) return MMFS_E_NULLPTR;
     if (((uintptr_t)q_rot | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)context) % 16 ||
-        ((uintptr_t)src_row | (uintptr_t)length) % 4 || (uintptr_t)bias % (bias_f32 ? 4 : 2))
+        ((uintptr_t)src_row | (uintptr_t)length) % 4 || !small_aligned((uintptr_t)bias, bias_f32))
         return MMFS_E_ALIGN;
     // a bias with a row per query whose rows all start 4 elements aligned is read 4 keys a lane
     const int bias_wide = bias && bias_query_stride && (uintptr_t)bias % (bias_f32 ? 16 : 8) == 0 && bias_query_stride % 4 == 0 &&

@@ -66,24 +66,22 @@
 //       |grad - ref| <= u_T |ref| + t_T + |g| (p ((2.5 |x - lse| + 2) e + E_lse) + 5 e |p - [i == label]| + 2^-126)
 //
 // Offsets are 64-bit: B L V passes 2^31 elements at ordinary batch sizes.
-#include "msda_host.h"
+#include "mmfs_attn_core.h"
 #include <hip/hip_runtime.h>
-#include <math.h>
 
 namespace mmfs {
 
 namespace {
+
+using attn::exp_hw;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kReduceThreads = 1024;
 constexpr int64_t kMaxRows = 1 << 22;           // B * L at most
 constexpr int64_t kMaxVocab = 1 << 24;
-constexpr float kLog2e = 1.44269504088896340736f;
 
 enum { kNone = 0, kSum = 1, kMean = 2 };        // ``reduction`` of the two entries
-
-__device__ __forceinline__ float exp_hw(float d) { return __builtin_amdgcn_exp2f(d * kLog2e); }
 
 // 0: ignored, 1: valid, 2: out of range
 __device__ __forceinline__ int label_class(int64_t label, int64_t ignore_index, int V)

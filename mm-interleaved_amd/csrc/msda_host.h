@@ -36,4 +36,7 @@ template <typename F> int by_type(int dtype, F &&f)
     return f(bf16_t());
 }
 
+// the same for an entry that serves the two 16-bit types alone (it has refused the others)
+template <typename F> int by_half_type(int dtype, F &&f) { return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t()); }
+
 }  // namespace mmfs

@@ -32,7 +32,7 @@ _lib.mmfs_llama_attn_prefill.restype = _int
 _lib.mmfs_llama_attn_prefill.argtypes = [_int] + [_vp] * 6 + [_int, _i64, _i64, _i64, ctypes.c_uint, _vp] + [_i64] * 5 + [_vp]
 _lib.mmfs_llama_attn_prefill_tiles.restype = _i64
 _lib.mmfs_llama_attn_prefill_tiles.argtypes = [_int]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_CODE = MSDA._DTYPE_CODE
 HEAD_DIM = 128
 # how the decode kernel cuts the keys: a wave's, a workgroup's (= a split's): where its paths change
 WAVE_KEYS, SPLIT_KEYS = int(_lib.mmfs_llama_attn_decode_keys(0)), int(_lib.mmfs_llama_attn_decode_keys(1))
@@ -87,6 +87,24 @@ def _check_cache(q, keys, values, length, src_row, what):
 def _plain(t):
     t = t.detach()
     return MSDA._aligned(t if t.is_contiguous() else t.contiguous())
+
+
+def _bias_args(bias, dev, dt):
+    """a mask as the kernels read it -> (tensor or None, dtype code, strides of the axes before the keys, keys): of fp32 or
+    of the inputs' type where it lies (anything else is cast to fp32), HF's 4-d mask without its head axis, the keys one
+    element apart and aligned to an element (else copied); an axis of length 1 has stride 0.  At least 2-d: the prefill
+    takes the batch and the query stride, the decode the batch stride alone."""
+    if bias is None:
+        return None, 0, (0, 0), 0
+    t = bias.detach()
+    if t.dim() == 4:
+        t = t[:, 0]
+    if t.dtype not in (torch.float32, dt) or t.device != dev:
+        t = t.to(device=dev, dtype=torch.float32)
+    if t.stride(-1) != 1 or t.data_ptr() % t.element_size():
+        t = t.clone(memory_format=torch.contiguous_format)
+    strides = tuple(0 if n == 1 else s for n, s in zip(t.shape[:-1], t.stride()[:-1]))
+    return t, _CODE[t.dtype], strides, t.shape[-1]
 
 
 def llama_rope_append(q, k, v, position_ids, cos, sin, keys, values, length, src_row):
@@ -145,17 +163,7 @@ def _attn_decode(q_rot, keys, values, length, src_row, bias=None, kv_bound=None)
     H, cap = keys.shape[1], keys.shape[2]
     kv_bound = cap if kv_bound is None else int(kv_bound)
     q_rot = _plain(q_rot)
-    bias_t, code, stride, blen = None, 0, 0, 0
-    if bias is not None:
-        bias_t = bias.detach()
-        if bias_t.dtype not in (torch.float32, dt) or bias_t.device != dev:
-            bias_t = bias_t.to(device=dev, dtype=torch.float32)
-        if bias_t.stride(-1) != 1 or bias_t.data_ptr() % bias_t.element_size():
-            bias_t = bias_t.clone(memory_format=torch.contiguous_format)
-        blen = bias_t.shape[-1]
-        shared = bias_t.shape[0] == 1 or bias_t.stride(0) == 0
-        stride = 0 if shared else bias_t.stride(0)
-        code = _CODE[bias_t.dtype]
+    bias_t, code, (stride, *_), blen = _bias_args(bias, dev, dt)
     out = torch.empty((B, 1, C), dtype=dt, device=dev)
     # the partials of the split walk (the caching allocator's, like ``out``: no device allocation in a steady loop)
     ws = torch.empty(max(_lib.mmfs_llama_attn_decode_workspace_bytes(B, H, kv_bound) // 4, 1), dtype=torch.float32, device=dev)
@@ -192,19 +200,7 @@ def _attn_prefill(q_rot, keys, values, length, src_row, bias=None, causal=False,
     B, Lq, C = q_rot.shape
     H, cap = keys.shape[1], keys.shape[2]
     q_rot = _plain(q_rot)
-    bias_t, code, batch_stride, query_stride, blen = None, 0, 0, 0, 0
-    if bias is not None:
-        bias_t = bias.detach()
-        if bias_t.dim() == 4:
-            bias_t = bias_t[:, 0]
-        if bias_t.dtype not in (torch.float32, dt) or bias_t.device != dev:
-            bias_t = bias_t.to(device=dev, dtype=torch.float32)
-        if bias_t.stride(-1) != 1 or bias_t.data_ptr() % bias_t.element_size():
-            bias_t = bias_t.clone(memory_format=torch.contiguous_format)
-        blen = bias_t.shape[-1]
-        batch_stride = 0 if bias_t.shape[0] == 1 else bias_t.stride(0)
-        query_stride = 0 if bias_t.shape[1] == 1 else bias_t.stride(1)
-        code = _CODE[bias_t.dtype]
+    bias_t, code, (batch_stride, query_stride), blen = _bias_args(bias, dev, dt)
     flags = (PREFILL_CAUSAL if causal else 0) | (PREFILL_VISIT_ALL if visit_all else 0)
     out = torch.empty((B, Lq, C), dtype=dt, device=dev)
     with MSDA._on_device(dev):

@@ -24,7 +24,7 @@ _lib.mmfs_qk_attn_forward.restype = _int
 _lib.mmfs_qk_attn_forward.argtypes = [_int] + [_vp] * 7 + [_int, _f32, _vp, _int, _i64] + [_vp] * 3 + [_i64] * 5 + [_vp]
 _lib.mmfs_qk_attn_backward.restype = _int
 _lib.mmfs_qk_attn_backward.argtypes = [_int] + [_vp] * 7 + [_int, _f32, _vp, _int, _i64] + [_vp] * 8 + [_i64] * 5 + [_vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+_CODE = MSDA._DTYPE_CODE
 HEAD_DIM = 64
 
 # kernel launches since import, for tests and tools that ask which route the module took
