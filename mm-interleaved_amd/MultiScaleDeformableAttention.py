@@ -28,6 +28,8 @@ import os
 import numpy as np
 import torch
 
+import mmfs_abi
+
 __all__ = ["ms_deform_attn_forward", "ms_deform_attn_backward", "register_level_tables", "library_path",
            "build_info", "check_level_table_status", "value_row_map", "quantize_bank_fp8", "quantize_bank_fp8_reference",
            "dequantize_bank_fp8", "FP8_BANK_DTYPE"]
@@ -43,65 +45,12 @@ if not os.path.exists(_LIB_PATH):
 _lib = ctypes.CDLL(_LIB_PATH)
 
 _ABI_VERSION = 14
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-
-_lib.mmfs_msda_abi_version.restype = _int
-_lib.mmfs_msda_abi_version.argtypes = []
-_lib.mmfs_msda_build_info.restype = ctypes.c_char_p
-_lib.mmfs_msda_build_info.argtypes = []
-_lib.mmfs_msda_status_string.restype = ctypes.c_char_p
-_lib.mmfs_msda_status_string.argtypes = [_int]
-_lib.mmfs_msda_forward.restype = _int
-_lib.mmfs_msda_forward.argtypes = [_int] + [_vp] * 6 + [_i64] * 7 + [_vp]
-_lib.mmfs_msda_forward_flags.restype = _int
-_lib.mmfs_msda_forward_flags.argtypes = [_int] + [_vp] * 6 + [_i64] * 7 + [ctypes.c_uint, _vp]
-_lib.mmfs_msda_forward_shared.restype = _int
-_lib.mmfs_msda_forward_shared.argtypes = [_int] + [_vp] * 6 + [_i64] * 2 + [_int] + [_i64] * 6 + [ctypes.c_uint, _vp]
-_lib.mmfs_bank_quantize_fp8.restype = _int
-_lib.mmfs_bank_quantize_fp8.argtypes = [_int, _vp] + [_i64] * 4 + [_vp, _vp, _vp]
-_lib.mmfs_msda_forward_fp8.restype = _int
-_lib.mmfs_msda_forward_fp8.argtypes = [_int] + [_vp] * 7 + [_i64] * 2 + [_int] + [_i64] * 6 + [_vp]
-_lib.mmfs_msda_backward.restype = _int
-_lib.mmfs_msda_backward.argtypes = [_int] + [_vp] * 10 + [_i64] * 8 + [ctypes.c_uint, _vp]
-_lib.mmfs_msda_backward_checked.restype = _int
-_lib.mmfs_msda_backward_checked.argtypes = [_int] + [_vp] * 10 + [_i64] * 8 + [ctypes.c_uint, _vp, _vp]
-_lib.mmfs_msda_backward_taps_fused.restype = _int
-_lib.mmfs_msda_backward_taps_fused.argtypes = [_int] + [_i64] * 7 + [ctypes.c_uint]
-_lib.mmfs_msda_backward_workspace_bytes.restype = _i64
-_lib.mmfs_msda_backward_workspace_bytes.argtypes = [_int] + [_i64] * 7 + [ctypes.c_uint]
-_lib.mmfs_msda_backward_taps.restype = _int
-_lib.mmfs_msda_backward_taps.argtypes = [_int] + [_vp] * 8 + [_i64] * 7 + [_vp]
-_lib.mmfs_msda_backward_value.restype = _int
-_lib.mmfs_msda_backward_value.argtypes = [_int] + [_vp] * 7 + [_i64] * 8 + [_vp]
-_lib.mmfs_msda_backward_value_prepare.restype = _int
-_lib.mmfs_msda_backward_value_prepare.argtypes = [_int] + [_vp] * 3 + [_i64] * 8 + [_vp]
-_lib.mmfs_msda_backward_value_run.restype = _int
-_lib.mmfs_msda_backward_value_run.argtypes = [_int] + [_vp] * 5 + [_i64] * 8 + [_vp]
-_lib.mmfs_msda_backward_value_sort.restype = _int
-_lib.mmfs_msda_backward_value_sort.argtypes = [_int] + [_vp] * 3 + [_i64] * 8 + [_vp]
-_lib.mmfs_msda_backward_value_reduce.restype = _int
-_lib.mmfs_msda_backward_value_reduce.argtypes = [_int] + [_vp] * 3 + [_i64] * 8 + [_vp]
-_lib.mmfs_msda_backward_hybrid_workspace_bytes.restype = _i64
-_lib.mmfs_msda_backward_hybrid_workspace_bytes.argtypes = [_int, _vp, _vp] + [_i64] * 7 + [ctypes.c_uint]
-_lib.mmfs_msda_backward_hybrid.restype = _int
-_lib.mmfs_msda_backward_hybrid.argtypes = [_int] + [_vp] * 12 + [_i64] * 8 + [ctypes.c_uint, ctypes.c_uint, _vp]
-_lib.mmfs_msda_backward_sorted_workspace_bytes.restype = _i64
-_lib.mmfs_msda_backward_sorted_workspace_bytes.argtypes = [_int] + [_i64] * 7 + [ctypes.c_uint]
-_lib.mmfs_msda_backward_sorted.restype = _int
-_lib.mmfs_msda_backward_sorted.argtypes = [_int] + [_vp] * 10 + [_i64] * 9 + [ctypes.c_uint, ctypes.c_uint, _vp]
-_lib.mmfs_msda_cast_from_f32.restype = _int
-_lib.mmfs_msda_cast_from_f32.argtypes = [_int, _vp, _vp, _i64, _vp]
-
-_lib.mmfs_env_reload.restype = None
-_lib.mmfs_env_reload.argtypes = []
-_lib.mmfs_env_knob.restype = _int
-_lib.mmfs_env_knob.argtypes = [_int] + [ctypes.POINTER(ctypes.c_char_p)] * 3
-
 if _lib.mmfs_msda_abi_version() != _ABI_VERSION:
     raise ImportError(f"{_LIB_PATH}: ABI version {_lib.mmfs_msda_abi_version()} != {_ABI_VERSION}")
+mmfs_abi.bind(_lib)                 # the signature of every entry point of include/mmfs_msda.h, from the one table
 
-# enum mmfs_dtype (include/mmfs_msda.h)
-_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
+# enum mmfs_dtype (include/mmfs_msda.h); _FLOAT_CODE: without fp64, what every entry point besides the op itself takes
+_DTYPE_CODE, _FLOAT_CODE = mmfs_abi.DTYPE_CODE, mmfs_abi.FLOAT_CODE
 
 
 def library_path():
@@ -284,6 +233,22 @@ def _launch(name, device, fn, *args):
     return status
 
 
+def _call(log_name, entry, device, *args, refuse_ok=False, what=None):
+    """One launch through the C ABI: ``_lib``'s ``entry`` (looked up now, by name) with ``args`` and the current stream of
+    ``device`` behind them, on that device, logged as ``log_name``.  A status other than 0 raises, named ``what``
+    (default: the entry point) -- except, with ``refuse_ok``, MMFS_E_UNSUPPORTED, which is returned: the caller then
+    takes its documented other path."""
+    with _on_device(device):
+        status = _launch(log_name, device, getattr(_lib, entry), *args, _stream(device))
+    if status != 0 and not (refuse_ok and status == _E_UNSUPPORTED):
+        _check(status, what or entry)
+    return status
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 # ---- level tables the shim has never seen are checked ON THE DEVICE by the backward (no device->host copy per
 # call).  A table the sorted backward cannot serve (overlapping / out-of-range / >= 65536-wide levels) gets the
 # reference's float-atomic scatter IN THE SAME CALL (csrc/msda_bwd_refused.hip: three launches that read the plan's
@@ -377,12 +342,9 @@ def quantize_bank_fp8(x):
     scale = torch.empty(*lead, C, dtype=torch.float32, device=x.device)
     K = lead[0] if len(lead) == 2 else 1
     Bv = lead[-1]
-    with _on_device(x.device):
-        status = _launch("bank_quantize_fp8", x.device, _lib.mmfs_bank_quantize_fp8, _DTYPE_CODE[x.dtype], x.data_ptr(),
-                         K, Bv, S, C, q.data_ptr(), scale.data_ptr(), _stream(x.device))
-    if status == _E_UNSUPPORTED:                     # (H*D not a multiple of 16: the rule, on the device)
-        return quantize_bank_fp8_reference(x)
-    _check(status, "quantize_bank_fp8")
+    if _call("bank_quantize_fp8", "mmfs_bank_quantize_fp8", x.device, _DTYPE_CODE[x.dtype], x.data_ptr(), K, Bv, S, C,
+             q.data_ptr(), scale.data_ptr(), refuse_ok=True, what="quantize_bank_fp8"):
+        return quantize_bank_fp8_reference(x)        # (H*D not a multiple of 16: the rule, on the device)
     return q, scale
 
 
@@ -412,17 +374,13 @@ def _forward_fp8(value, value_scale, spatial_shapes, level_start_index, sampling
         sampling_loc = sampling_loc.to(dt)
     value, value_scale = _aligned(value), _aligned(value_scale)
     out = torch.empty((B, Nq, H * D), dtype=dt, device=value.device)
-    with _on_device(value.device):
-        status = _launch(
-            "msda_fwd", value.device, _lib.mmfs_msda_forward_fp8, _DTYPE_CODE[dt], value.data_ptr(), value_scale.data_ptr(),
-            spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-            out.data_ptr(), B, Bv, layout, S, H, D, L, Nq, P, _stream(value.device))
-    if status == _E_UNSUPPORTED:
+    if _call("msda_fwd", "mmfs_msda_forward_fp8", value.device, _DTYPE_CODE[dt], value.data_ptr(), value_scale.data_ptr(),
+             spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+             out.data_ptr(), B, Bv, layout, S, H, D, L, Nq, P, refuse_ok=True, what="ms_deform_attn_forward"):
         # a head width the fp8 kernels do not serve (D not 16 * 2^k, k <= 4): the documented slow path -- the bank
         # dequantised to the output type, then the ordinary forward
         return ms_deform_attn_forward(dequantize_bank_fp8(value, value_scale, dt), spatial_shapes, level_start_index,
                                       sampling_loc, attn_weight, im2col_step, value_repeat=value_repeat)
-    _check(status, "ms_deform_attn_forward")
     return out
 
 
@@ -455,29 +413,20 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     sampling_loc, attn_weight = _same_dtype(value, sampling_loc, attn_weight)
     value = _aligned(value)
     out = torch.empty((B, Nq, H * D), dtype=value.dtype, device=value.device)
-    code = _DTYPE_CODE[value.dtype]
-    with _on_device(value.device):
-        stream = _stream(value.device)
-
-        def launch(name, flags):
-            if value_repeat is None:
-                return _launch(
-                    name, value.device, _lib.mmfs_msda_forward_flags, code, value.data_ptr(), spatial_shapes.data_ptr(),
-                    level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                    out.data_ptr(), B, S, H, D, L, Nq, P, flags, stream)
-            return _launch(
-                name, value.device, _lib.mmfs_msda_forward_shared, code, value.data_ptr(), spatial_shapes.data_ptr(),
-                level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                out.data_ptr(), B, Bv, _VALUE_REPEAT[value_repeat], S, H, D, L, Nq, P, flags, stream)
-        if _fwd_algo in ("lds", "slices", "waves") and S * H * D * value.element_size() > _MAX_SLAB_BYTES:
-            # none of the kernels that can be asked for by name takes a (b) slab its 32-bit row offsets cannot span
-            # (csrc/msda_device.h, kMaxSlabBytes): the row gather's flat-address kernel serves the call, as it does under
-            # "auto" and as the backward does for its named LDS-levels kernel -- decided here, on the size alone, whatever
-            # else the named kernel would have refused.  Under the limit a named kernel's refusal raises, as before.
-            status = launch("msda_fwd_gather", _FWD_FLAGS["gather"])
-        else:
-            status = launch("msda_fwd", _FWD_FLAGS[_fwd_algo])
-    _check(status, "ms_deform_attn_forward")
+    if value_repeat is None:
+        entry, bank = "mmfs_msda_forward_flags", ()
+    else:
+        entry, bank = "mmfs_msda_forward_shared", (Bv, _VALUE_REPEAT[value_repeat])
+    name, algo = "msda_fwd", _fwd_algo
+    if algo in ("lds", "slices", "waves") and S * H * D * value.element_size() > _MAX_SLAB_BYTES:
+        # none of the kernels that can be asked for by name takes a (b) slab its 32-bit row offsets cannot span
+        # (csrc/msda_device.h, kMaxSlabBytes): the row gather's flat-address kernel serves the call, as it does under
+        # "auto" and as the backward does for its named LDS-levels kernel -- decided here, on the size alone, whatever
+        # else the named kernel would have refused.  Under the limit a named kernel's refusal raises, as before.
+        name, algo = "msda_fwd_gather", "gather"
+    _call(name, entry, value.device, _DTYPE_CODE[value.dtype], value.data_ptr(), spatial_shapes.data_ptr(),
+          level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(), B, *bank,
+          S, H, D, L, Nq, P, _FWD_FLAGS[algo], what="ms_deform_attn_forward")
     return out
 
 

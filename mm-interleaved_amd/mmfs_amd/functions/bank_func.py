@@ -12,12 +12,7 @@ from torch.autograd.function import once_differentiable
 
 import MultiScaleDeformableAttention as MSDA
 
-_lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-for _f in (_lib.mmfs_bank_gather, _lib.mmfs_bank_scatter):
-    _f.restype = _int
-    _f.argtypes = [_int, _int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 MAX_LEVELS, MAX_SLOTS = 8, 65535
 
 
@@ -47,11 +42,8 @@ class BankGatherFunction(Function):
         S = sum(f.shape[2] * f.shape[3] for f in levels)
         bank = torch.empty((n_slots, S, C), dtype=f0.dtype, device=f0.device)
         ptrs, hw = _tables(levels)
-        with torch.cuda.device(f0.device):
-            rc = MSDA._launch("mmfs_bank_gather", f0.device, _lib.mmfs_bank_gather, _CODE[f0.dtype], len(levels),
-                              ctypes.cast(ptrs, _vp), ctypes.cast(hw, _vp), src_index.data_ptr(), bank.data_ptr(),
-                              n_img, C, n_slots, MSDA._stream(f0.device))
-        MSDA._check(rc, "mmfs_bank_gather")
+        MSDA._call("mmfs_bank_gather", "mmfs_bank_gather", f0.device, _CODE[f0.dtype], len(levels), ptrs, hw,
+                   src_index.data_ptr(), bank.data_ptr(), n_img, C, n_slots)
         ctx.save_for_backward(src_index)
         ctx.level_shapes = [tuple(f.shape) for f in levels]
         return bank
@@ -64,9 +56,6 @@ class BankGatherFunction(Function):
         grads = [torch.empty(s, dtype=grad_bank.dtype, device=grad_bank.device) for s in ctx.level_shapes]
         n_img, C = ctx.level_shapes[0][:2]
         ptrs, hw = _tables(grads)
-        with torch.cuda.device(grad_bank.device):
-            rc = MSDA._launch("mmfs_bank_scatter", grad_bank.device, _lib.mmfs_bank_scatter, _CODE[grad_bank.dtype],
-                              len(grads), ctypes.cast(ptrs, _vp), ctypes.cast(hw, _vp), src_index.data_ptr(),
-                              grad_bank.data_ptr(), n_img, C, src_index.numel(), MSDA._stream(grad_bank.device))
-        MSDA._check(rc, "mmfs_bank_scatter")
+        MSDA._call("mmfs_bank_scatter", "mmfs_bank_scatter", grad_bank.device, _CODE[grad_bank.dtype], len(grads), ptrs, hw,
+                   src_index.data_ptr(), grad_bank.data_ptr(), n_img, C, src_index.numel())
         return (None, *grads)

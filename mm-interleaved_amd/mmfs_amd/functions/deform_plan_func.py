@@ -9,8 +9,6 @@ for calls without gradients.  C ABI: ``mmfs_deform_plan_forward`` / ``mmfs_defor
 mathematics with framework ops -- that is NOT a CPU fallback of the sampling op, only of this front end, and it is
 what the CPU parity tests of the module and of the adapter blocks exercise.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -18,16 +16,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_deform_plan_supported.restype = _int
-_lib.mmfs_deform_plan_supported.argtypes = [_int] + [_i64] * 4
-_lib.mmfs_deform_plan_forward.restype = _int
-_lib.mmfs_deform_plan_forward.argtypes = [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp] + [_i64] * 8 + [_vp]
-_lib.mmfs_deform_plan_backward.restype = _int
-_lib.mmfs_deform_plan_backward.argtypes = [_int] + [_vp] * 7 + [_i64] * 2 + [_i64] * 8 + [_vp]
-_lib.mmfs_deform_sample_forward.restype = _int
-_lib.mmfs_deform_sample_forward.argtypes = [_int] + [_vp] * 5 + [_i64] * 2 + [_vp, _vp] + [_i64] * 10 + [_vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 
 
 def _ref_ok(reference_points, N, L):
@@ -83,10 +72,8 @@ class DeformPlanFunction(Function):
         attn = torch.empty((N, Lq, H, L, P), dtype=dt, device=dev)
         dims = (N, Lq, H, L, P, Nr, Lref, R)
         off, logit, p_off, p_att, ld_off, ld_att = _heads(both, n_off)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("deform_plan_fwd", dev, _lib.mmfs_deform_plan_forward, _CODE[dt], p_off, p_att, ld_off, ld_att,
-                              ref.data_ptr(), shapes.data_ptr(), loc.data_ptr(), attn.data_ptr(), *dims, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_deform_plan_forward")
+        MSDA._call("deform_plan_fwd", "mmfs_deform_plan_forward", dev, _CODE[dt], p_off, p_att, ld_off, ld_att,
+                   ref.data_ptr(), shapes.data_ptr(), loc.data_ptr(), attn.data_ptr(), *dims)
         ctx.save_for_backward(attn, ref, shapes)
         ctx.dims = dims
         return loc, attn
@@ -108,11 +95,8 @@ class DeformPlanFunction(Function):
             d_off = torch.empty((N, Lq, n_off), dtype=dt, device=dev)
             d_att = torch.empty((N, Lq, C - n_off), dtype=dt, device=dev)
             p_off, p_att, ld = d_off.data_ptr(), d_att.data_ptr(), 0
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("deform_plan_bwd", dev, _lib.mmfs_deform_plan_backward, _CODE[dt], g_loc.data_ptr(),
-                              g_attn.data_ptr(), attn.data_ptr(), ref.data_ptr(), shapes.data_ptr(), p_off, p_att, ld, ld,
-                              *ctx.dims, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_deform_plan_backward")
+        MSDA._call("deform_plan_bwd", "mmfs_deform_plan_backward", dev, _CODE[dt], g_loc.data_ptr(), g_attn.data_ptr(),
+                   attn.data_ptr(), ref.data_ptr(), shapes.data_ptr(), p_off, p_att, ld, ld, *ctx.dims)
         return (d_both if stacked else torch.cat((d_off, d_att), -1)), None, None, None, None, None
 
 
@@ -135,11 +119,8 @@ def deform_sample_forward(value, shapes, start, both, ref, H, L, P):
     value, both, start = MSDA._aligned(value.contiguous()), both.contiguous(), start.contiguous()
     out = torch.empty((N, Lq, H * D), dtype=dt, device=dev)
     off, logit, p_off, p_att, ld_off, ld_att = _heads(both, n_off)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("deform_sample_fwd", dev, _lib.mmfs_deform_sample_forward, _CODE[dt], value.data_ptr(),
-                          shapes.data_ptr(), start.data_ptr(), p_off, p_att, ld_off, ld_att, ref.data_ptr(), out.data_ptr(), N, S, Lq, H, D, L, P, ref.shape[0], ref.shape[2],
-                          ref.shape[3], MSDA._stream(dev))
-    if rc == MSDA._E_UNSUPPORTED:
+    if MSDA._call("deform_sample_fwd", "mmfs_deform_sample_forward", dev, _CODE[dt], value.data_ptr(), shapes.data_ptr(),
+                  start.data_ptr(), p_off, p_att, ld_off, ld_att, ref.data_ptr(), out.data_ptr(), N, S, Lq, H, D, L, P,
+                  ref.shape[0], ref.shape[2], ref.shape[3], refuse_ok=True):
         return None
-    MSDA._check(rc, "mmfs_deform_sample_forward")
     return out

@@ -16,16 +16,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_dwconv_tokens_supported.restype = _int
-_lib.mmfs_dwconv_tokens_supported.argtypes = [_int, _i64, _i64, _int]
-_lib.mmfs_dwconv_tokens_forward.restype = _int
-_lib.mmfs_dwconv_tokens_forward.argtypes = [_int] + [_vp] * 6 + [_i64] * 4 + [_int, _vp]
-_lib.mmfs_dwconv_tokens_backward_workspace_bytes.restype = _i64
-_lib.mmfs_dwconv_tokens_backward_workspace_bytes.argtypes = [_int, _vp] + [_i64] * 4 + [_int]
-_lib.mmfs_dwconv_tokens_backward.restype = _int
-_lib.mmfs_dwconv_tokens_backward.argtypes = [_int] + [_vp] * 9 + [_i64] * 4 + [_int, _vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 ACT = {"none": 0, "gelu": 1}
 
 # kernel calls since import, for tests and tools that ask which route a block took
@@ -39,7 +30,7 @@ def _levels(level_hw):
     key = tuple((int(h), int(w)) for h, w in level_hw)
     arr = _host_levels.get(key)
     if arr is None:
-        arr = _host_levels[key] = (_i64 * (2 * len(key)))(*[v for hw in key for v in hw])
+        arr = _host_levels[key] = (ctypes.c_int64 * (2 * len(key)))(*[v for hw in key for v in hw])
     return key, arr
 
 
@@ -70,11 +61,8 @@ class DWConvTokensFunction(Function):
         needs_grad = any(ctx.needs_input_grad[:3])
         out = torch.empty((B, N, C), dtype=dt, device=dev)
         pre = torch.empty((B, N, C), dtype=dt, device=dev) if needs_grad and code else None
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("dwconv_fwd", dev, _lib.mmfs_dwconv_tokens_forward, _CODE[dt], x.data_ptr(), weight.data_ptr(),
-                              None if bias is None else bias.data_ptr(), out.data_ptr(),
-                              None if pre is None else pre.data_ptr(), arr, B, N, C, len(key), code, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_dwconv_tokens_forward")
+        MSDA._call("dwconv_fwd", "mmfs_dwconv_tokens_forward", dev, _CODE[dt], x.data_ptr(), weight.data_ptr(),
+                   MSDA._ptr(bias), out.data_ptr(), MSDA._ptr(pre), arr, B, N, C, len(key), code)
         launches["forward"] += 1
         if needs_grad:
             ctx.save_for_backward(x, weight, pre)
@@ -101,11 +89,8 @@ class DWConvTokensFunction(Function):
         nbytes = _lib.mmfs_dwconv_tokens_backward_workspace_bytes(_CODE[dt], arr, B, N, C, len(key), code)
         MSDA._check(min(nbytes, 0), "mmfs_dwconv_tokens_backward_workspace_bytes")
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("dwconv_bwd", dev, _lib.mmfs_dwconv_tokens_backward, _CODE[dt], g.data_ptr(), x.data_ptr(),
-                              None if pre is None else pre.data_ptr(), weight.data_ptr(), gx.data_ptr(), gw.data_ptr(),
-                              None if gb is None else gb.data_ptr(), ws.data_ptr(), arr, B, N, C, len(key), code,
-                              MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_dwconv_tokens_backward")
+        MSDA._call("dwconv_bwd", "mmfs_dwconv_tokens_backward", dev, _CODE[dt], g.data_ptr(), x.data_ptr(), MSDA._ptr(pre),
+                   weight.data_ptr(), gx.data_ptr(), gw.data_ptr(), MSDA._ptr(gb), ws.data_ptr(), arr, B, N, C, len(key),
+                   code)
         launches["backward"] += 1
         return gx, gw, gb, None, None

@@ -3,22 +3,13 @@ gfx950 kernel (csrc/mmfs_linear.hip; C ABI ``mmfs_linear_small``, include/mmfs_m
 MMFS layer (mm_interleaved/models/utils/ops/modules/mmfs.py:174-176, 274) are at 4 tokens.  Taken when no gradient is
 wanted, for device tensors of one 16-bit storage type with at most 8 rows; anything else is ``F.linear`` (which is
 what the CPU tests run).  fp32 accumulation, bias added in fp32, one rounding: the roundings of the library call."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_linear_small_supported.restype = _int
-_lib.mmfs_linear_small_supported.argtypes = [_int, _i64, _i64, _i64]
-_lib.mmfs_linear_small.restype = _int
-_lib.mmfs_linear_small.argtypes = [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]
-_lib.mmfs_linear_small_add.restype = _int
-_lib.mmfs_linear_small_add.argtypes = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp]
-_CODE = {torch.float16: 1, torch.bfloat16: 2}
+_CODE = {t: MSDA._DTYPE_CODE[t] for t in (torch.float16, torch.bfloat16)}       # the types served: 16-bit storage only
 _ok = {}
 enabled = True          # (measurements: False keeps every call on F.linear)
 
@@ -47,12 +38,8 @@ def small_linear(x, weight, bias=None, residual=None):
         return plain()
     y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
     b = bias.contiguous() if bias is not None else None
-    with MSDA._on_device(x.device):
-        rc = MSDA._launch("mmfs_linear_small", x.device, _lib.mmfs_linear_small_add, _CODE[x.dtype], x.data_ptr(),
-                          weight.data_ptr(), b.data_ptr() if b is not None else None,
-                          residual.data_ptr() if residual is not None else None, y.data_ptr(), M, N, K, K, N, N,
-                          MSDA._stream(x.device))
-    MSDA._check(rc, "mmfs_linear_small")
+    MSDA._call("mmfs_linear_small", "mmfs_linear_small_add", x.device, _CODE[x.dtype], x.data_ptr(), weight.data_ptr(),
+               MSDA._ptr(b), MSDA._ptr(residual), y.data_ptr(), M, N, K, K, N, N, what="mmfs_linear_small")
     return y
 
 

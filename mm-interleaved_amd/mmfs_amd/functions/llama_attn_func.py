@@ -6,32 +6,11 @@ nothing here is differentiable.  Nothing reads a value back from the device: a s
 
 ``mmfs_amd.llama_attn`` holds the cache (``LlamaKVCache``) and the module (``LlamaSelfAttention``) built on these.
 """
-import ctypes
-
 import torch
 
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-if not hasattr(_lib, "mmfs_llama_attn_decode"):         # (additive at ABI 14: detected by symbol)
-    raise ImportError(f"{MSDA.library_path()} has no mmfs_llama_attn_decode: rebuild the library")
-_lib.mmfs_llama_attn_supported.restype = _int
-_lib.mmfs_llama_attn_supported.argtypes = [_int] + [_i64] * 3
-_lib.mmfs_llama_attn_rope_append.restype = _int
-_lib.mmfs_llama_attn_rope_append.argtypes = [_int] + [_vp] * 6 + [_i64] + [_vp] * 5 + [_i64] * 5 + [_vp]
-_lib.mmfs_llama_attn_decode_keys.restype = _i64
-_lib.mmfs_llama_attn_decode_keys.argtypes = [_int]
-_lib.mmfs_llama_attn_decode_workspace_bytes.restype = _i64
-_lib.mmfs_llama_attn_decode_workspace_bytes.argtypes = [_i64] * 3
-_lib.mmfs_llama_attn_decode.restype = _int
-_lib.mmfs_llama_attn_decode.argtypes = [_int] + [_vp] * 6 + [_int, _i64, _i64] + [_vp] * 2 + [_i64] * 5 + [_vp]
-if not hasattr(_lib, "mmfs_llama_attn_prefill"):        # (additive at ABI 14 as well)
-    raise ImportError(f"{MSDA.library_path()} has no mmfs_llama_attn_prefill: rebuild the library")
-_lib.mmfs_llama_attn_prefill.restype = _int
-_lib.mmfs_llama_attn_prefill.argtypes = [_int] + [_vp] * 6 + [_int, _i64, _i64, _i64, ctypes.c_uint, _vp] + [_i64] * 5 + [_vp]
-_lib.mmfs_llama_attn_prefill_tiles.restype = _i64
-_lib.mmfs_llama_attn_prefill_tiles.argtypes = [_int]
 _CODE = MSDA._DTYPE_CODE
 HEAD_DIM = 128
 # how the decode kernel cuts the keys: a wave's, a workgroup's (= a split's): where its paths change
@@ -134,12 +113,9 @@ def _rope_append(q, k, v, position_ids, cos, sin, keys, values, length, src_row)
     if pos.dtype != torch.int64 or pos.device != dev or not pos.is_contiguous() or tuple(pos.shape) != (B, Lq):
         pos = pos.to(device=dev, dtype=torch.int64).expand(B, Lq).contiguous()
     q_rot = torch.empty((B, Lq, C), dtype=dt, device=dev)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("llama_rope_append", dev, _lib.mmfs_llama_attn_rope_append, _CODE[dt], q.data_ptr(), k.data_ptr(),
-                          v.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], length.data_ptr(),
-                          q_rot.data_ptr(), keys.data_ptr(), values.data_ptr(), src_row.data_ptr(), B, Lq, H, C // H, cap,
-                          MSDA._stream(dev))
-    MSDA._check(rc, "mmfs_llama_attn_rope_append")
+    MSDA._call("llama_rope_append", "mmfs_llama_attn_rope_append", dev, _CODE[dt], q.data_ptr(), k.data_ptr(), v.data_ptr(),
+               pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], length.data_ptr(), q_rot.data_ptr(),
+               keys.data_ptr(), values.data_ptr(), src_row.data_ptr(), B, Lq, H, C // H, cap)
     launches["append"] += 1
     return q_rot
 
@@ -167,12 +143,9 @@ def _attn_decode(q_rot, keys, values, length, src_row, bias=None, kv_bound=None)
     out = torch.empty((B, 1, C), dtype=dt, device=dev)
     # the partials of the split walk (the caching allocator's, like ``out``: no device allocation in a steady loop)
     ws = torch.empty(max(_lib.mmfs_llama_attn_decode_workspace_bytes(B, H, kv_bound) // 4, 1), dtype=torch.float32, device=dev)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("llama_attn_decode", dev, _lib.mmfs_llama_attn_decode, _CODE[dt], q_rot.data_ptr(),
-                          keys.data_ptr(), values.data_ptr(), src_row.data_ptr(), length.data_ptr(),
-                          None if bias_t is None else bias_t.data_ptr(), code, stride, blen, out.data_ptr(), ws.data_ptr(),
-                          B, H, C // H, cap, kv_bound, MSDA._stream(dev))
-    MSDA._check(rc, "mmfs_llama_attn_decode")
+    MSDA._call("llama_attn_decode", "mmfs_llama_attn_decode", dev, _CODE[dt], q_rot.data_ptr(), keys.data_ptr(),
+               values.data_ptr(), src_row.data_ptr(), length.data_ptr(), MSDA._ptr(bias_t), code, stride, blen,
+               out.data_ptr(), ws.data_ptr(), B, H, C // H, cap, kv_bound)
     launches["decode"] += 2
     return out
 
@@ -203,11 +176,8 @@ def _attn_prefill(q_rot, keys, values, length, src_row, bias=None, causal=False,
     bias_t, code, (batch_stride, query_stride), blen = _bias_args(bias, dev, dt)
     flags = (PREFILL_CAUSAL if causal else 0) | (PREFILL_VISIT_ALL if visit_all else 0)
     out = torch.empty((B, Lq, C), dtype=dt, device=dev)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("llama_attn_prefill", dev, _lib.mmfs_llama_attn_prefill, _CODE[dt], q_rot.data_ptr(), keys.data_ptr(),
-                          values.data_ptr(), src_row.data_ptr(), length.data_ptr(),
-                          None if bias_t is None else bias_t.data_ptr(), code, batch_stride, query_stride, blen, flags,
-                          out.data_ptr(), B, Lq, H, C // H, cap, MSDA._stream(dev))
-    MSDA._check(rc, "mmfs_llama_attn_prefill")
+    MSDA._call("llama_attn_prefill", "mmfs_llama_attn_prefill", dev, _CODE[dt], q_rot.data_ptr(), keys.data_ptr(),
+               values.data_ptr(), src_row.data_ptr(), length.data_ptr(), MSDA._ptr(bias_t), code, batch_stride, query_stride,
+               blen, flags, out.data_ptr(), B, Lq, H, C // H, cap)
     launches["prefill"] += 1
     return out

@@ -8,8 +8,6 @@ reference points shared by all levels, P in {4, 8, 16}, n_images * n_levels <= 6
 mathematics with framework ops -- that is NOT a CPU fallback of the sampling op, only of this
 front-end, and it is what the CPU parity tests of the module exercise.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -17,30 +15,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_plan_forward.restype = _int
-_lib.mmfs_plan_forward.argtypes = [_int] + [_vp] * 11 + [_i64] * 9 + [_vp]
-_lib.mmfs_plan_backward.restype = _int
-_lib.mmfs_plan_backward.argtypes = [_int] + [_vp] * 12 + [_i64] * 9 + [_vp]
-_lib.mmfs_sample_forward.restype = _int
-_lib.mmfs_sample_forward.argtypes = [_int] + [_vp] * 12 + [_i64] * 11 + [_vp]
-_lib.mmfs_sample_forward_token.restype = _int
-_lib.mmfs_sample_forward_token.argtypes = [_int] + [_vp] * 13 + [_i64] * 11 + [_vp]
-_lib.mmfs_sample_forward_heads.restype = _int
-_lib.mmfs_sample_forward_heads.argtypes = [_int] + [_vp] * 5 + [_i64] * 2 + [_vp] * 8 + [_i64] * 11 + [_vp]
-_lib.mmfs_sample_forward_heads_shared.restype = _int
-_lib.mmfs_sample_forward_heads_shared.argtypes = ([_int] + [_vp] * 5 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
-                                                  + [_i64] * 10 + [_vp])
-_lib.mmfs_plan_forward_heads.restype = _int
-_lib.mmfs_plan_forward_heads.argtypes = [_int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 7 + [_i64] * 9 + [_vp]
-_lib.mmfs_plan_backward_heads.restype = _int
-_lib.mmfs_plan_backward_heads.argtypes = [_int] + [_vp] * 8 + [_vp, _vp, _i64, _i64, _int, _vp, _vp, _i64, _i64] + [_i64] * 9 + [_vp]
-_lib.mmfs_sample_forward_heads_fp8.restype = _int
-_lib.mmfs_sample_forward_heads_fp8.argtypes = ([_int] + [_vp] * 6 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
-                                               + [_i64] * 10 + [_vp])
-_lib.mmfs_sample_forward_groups.restype = _int
-_lib.mmfs_sample_forward_groups.argtypes = [_int] + [_i64] * 4
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 
 
 def mmfs_plan_supported(query, reference_points, n_levels, n_points, n_images):
@@ -68,12 +43,9 @@ class MMFSPlanFunction(Function):
         attn = torch.empty((N, Lq, H, n * L, P), dtype=dt, device=dev)
         sink = torch.empty((N, Lq, H), dtype=torch.float32, device=dev)
         dims = (N, Lq, H, L, P, n, M, Lr, Nr)
-        with torch.cuda.device(dev):
-            rc = MSDA._launch("mmfs_plan_fwd", dev, _lib.mmfs_plan_forward, _CODE[dt], off_q.data_ptr(),
-                              att_q.data_ptr(), off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(),
-                              ref.data_ptr(), shapes.data_ptr(), ratios.data_ptr(), loc.data_ptr(),
-                              attn.data_ptr(), sink.data_ptr(), *dims, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_plan_forward")
+        MSDA._call("mmfs_plan_fwd", "mmfs_plan_forward", dev, _CODE[dt], off_q.data_ptr(), att_q.data_ptr(),
+                   off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(), shapes.data_ptr(),
+                   ratios.data_ptr(), loc.data_ptr(), attn.data_ptr(), sink.data_ptr(), *dims)
         ctx.save_for_backward(attn, sink, relpos, shapes, ratios)
         ctx.dims = dims
         ctx.shapes_in = (off_q.shape, att_q.shape, off_tab.shape, att_tab.shape)
@@ -92,13 +64,10 @@ class MMFSPlanFunction(Function):
         d_att_q = torch.empty((N, Lq, H * L * P), dtype=torch.float32, device=dev)
         d_off_tab = torch.zeros((M, H * P * 2), dtype=torch.float32, device=dev)
         d_att_tab = torch.zeros((M, H * L * P), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = MSDA._launch("mmfs_plan_bwd", dev, _lib.mmfs_plan_backward, _CODE[dt], g_loc.data_ptr(),
-                              g_attn.data_ptr(), g_sink.data_ptr() if g_sink is not None else None,
-                              attn.data_ptr(), sink.data_ptr(), relpos.data_ptr(), shapes.data_ptr(),
-                              ratios.data_ptr(), d_off_q.data_ptr(), d_att_q.data_ptr(), d_off_tab.data_ptr(),
-                              d_att_tab.data_ptr(), N, Lq, H, L, P, n, M, Lr, Nr, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_plan_backward")
+        MSDA._call("mmfs_plan_bwd", "mmfs_plan_backward", dev, _CODE[dt], g_loc.data_ptr(), g_attn.data_ptr(),
+                   MSDA._ptr(g_sink), attn.data_ptr(), sink.data_ptr(), relpos.data_ptr(), shapes.data_ptr(),
+                   ratios.data_ptr(), d_off_q.data_ptr(), d_att_q.data_ptr(), d_off_tab.data_ptr(), d_att_tab.data_ptr(),
+                   *ctx.dims)
         s0, s1, s2, s3 = ctx.shapes_in
         return (d_off_q.to(dt).reshape(s0), d_att_q.to(dt).reshape(s1), d_off_tab.to(dt).reshape(s2),
                 d_att_tab.to(dt).reshape(s3), None, None, None, None, None, None, None)
@@ -128,12 +97,10 @@ class MMFSHeadsPlanFunction(Function):
         attn = torch.empty((N, Lq, H, n * L, P), dtype=dt, device=dev)
         sink = torch.empty((N, Lq, H), dtype=torch.float32, device=dev)
         dims = (N, Lq, H, L, P, n, M, Lr, Nr)
-        with torch.cuda.device(dev):
-            rc = MSDA._launch("mmfs_plan_fwd", dev, _lib.mmfs_plan_forward_heads, _CODE[dt], both.data_ptr(),
-                              both.data_ptr() + n_off * es, C, C, tabs.data_ptr(), tabs.data_ptr() + n_off * es, C, C,
-                              relpos.data_ptr(), ref.data_ptr(), shapes.data_ptr(), ratios.data_ptr(), loc.data_ptr(),
-                              attn.data_ptr(), sink.data_ptr(), *dims, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_plan_forward_heads")
+        MSDA._call("mmfs_plan_fwd", "mmfs_plan_forward_heads", dev, _CODE[dt], both.data_ptr(),
+                   both.data_ptr() + n_off * es, C, C, tabs.data_ptr(), tabs.data_ptr() + n_off * es, C, C,
+                   relpos.data_ptr(), ref.data_ptr(), shapes.data_ptr(), ratios.data_ptr(), loc.data_ptr(),
+                   attn.data_ptr(), sink.data_ptr(), *dims)
         ctx.save_for_backward(attn, sink, relpos, shapes, ratios)
         ctx.dims = dims
         return loc, attn, sink
@@ -151,14 +118,10 @@ class MMFSHeadsPlanFunction(Function):
         d_both = torch.empty((N, Lq, C), dtype=dt, device=dev)
         d_tabs = torch.zeros((M, C), dtype=torch.float32, device=dev)
         es = d_both.element_size()
-        with torch.cuda.device(dev):
-            rc = MSDA._launch("mmfs_plan_bwd", dev, _lib.mmfs_plan_backward_heads, _CODE[dt], g_loc.data_ptr(),
-                              g_attn.data_ptr(), g_sink.data_ptr() if g_sink is not None else None,
-                              attn.data_ptr(), sink.data_ptr(), relpos.data_ptr(), shapes.data_ptr(),
-                              ratios.data_ptr(), d_both.data_ptr(), d_both.data_ptr() + n_off * es, C, C, 1,
-                              d_tabs.data_ptr(), d_tabs.data_ptr() + n_off * 4, C, C,
-                              N, Lq, H, L, P, n, M, Lr, Nr, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_plan_backward_heads")
+        MSDA._call("mmfs_plan_bwd", "mmfs_plan_backward_heads", dev, _CODE[dt], g_loc.data_ptr(), g_attn.data_ptr(),
+                   MSDA._ptr(g_sink), attn.data_ptr(), sink.data_ptr(), relpos.data_ptr(), shapes.data_ptr(),
+                   ratios.data_ptr(), d_both.data_ptr(), d_both.data_ptr() + n_off * es, C, C, 1,
+                   d_tabs.data_ptr(), d_tabs.data_ptr() + n_off * 4, C, C, *ctx.dims)
         return d_both, d_tabs.to(dt), None, None, None, None, None, None, None
 
 
@@ -231,31 +194,19 @@ def mmfs_sample_forward(value, shapes, start, off_q, att_q, off_tab, att_tab, re
         if token.dtype != dt or token.numel() != Hh * D:
             return None
         tok = MSDA._aligned(token.reshape(Hh, D).contiguous())
-    with torch.cuda.device(dev):
-        if fp8:
-            MSDA._require(value_scale.dtype == torch.float32 and tuple(value_scale.shape) == (Nv, Hh * D) and value_scale.is_cuda,
-                          f"value_scale must be fp32 [{Nv}, {Hh * D}] on the bank's device")
-            value_scale = MSDA._aligned(value_scale.contiguous())
-            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads_fp8, _CODE[dt], value.data_ptr(),
-                              value_scale.data_ptr(), shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(),
-                              ld_off, ld_att, off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
-                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
-                              sink.data_ptr(), N, Nv, MSDA._VALUE_REPEAT[value_repeat or "tile"], S, Lq, Hh, D, L, P, n, M,
-                              Lr, Nr, MSDA._stream(dev))
-        elif value_repeat is None:
-            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads, _CODE[dt], value.data_ptr(),
-                              shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
-                              off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
-                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
-                              sink.data_ptr(), N, S, Lq, Hh, D, L, P, n, M, Lr, Nr, MSDA._stream(dev))
-        else:
-            rc = MSDA._launch("mmfs_sample_fwd", dev, _lib.mmfs_sample_forward_heads_shared, _CODE[dt], value.data_ptr(),
-                              shapes.data_ptr(), start.data_ptr(), off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att,
-                              off_tab.data_ptr(), att_tab.data_ptr(), relpos.data_ptr(), ref.data_ptr(),
-                              ratios.data_ptr(), tok.data_ptr() if tok is not None else None, out.data_ptr(),
-                              sink.data_ptr(), N, Nv, MSDA._VALUE_REPEAT[value_repeat], S, Lq, Hh, D, L, P, n, M, Lr, Nr,
-                              MSDA._stream(dev))
-    if rc == MSDA._E_UNSUPPORTED:
+    # the bank's part of the argument list: none | how Nv rows serve N | that, and the scales behind the bank
+    entry, scale, bank = "mmfs_sample_forward_heads", (), ()
+    if fp8:
+        MSDA._require(value_scale.dtype == torch.float32 and tuple(value_scale.shape) == (Nv, Hh * D) and value_scale.is_cuda,
+                      f"value_scale must be fp32 [{Nv}, {Hh * D}] on the bank's device")
+        value_scale = MSDA._aligned(value_scale.contiguous())
+        entry, scale = "mmfs_sample_forward_heads_fp8", (value_scale.data_ptr(),)
+        bank = (Nv, MSDA._VALUE_REPEAT[value_repeat or "tile"])
+    elif value_repeat is not None:
+        entry, bank = "mmfs_sample_forward_heads_shared", (Nv, MSDA._VALUE_REPEAT[value_repeat])
+    if MSDA._call("mmfs_sample_fwd", entry, dev, _CODE[dt], value.data_ptr(), *scale, shapes.data_ptr(), start.data_ptr(),
+                  off_q.data_ptr(), att_q.data_ptr(), ld_off, ld_att, off_tab.data_ptr(), att_tab.data_ptr(),
+                  relpos.data_ptr(), ref.data_ptr(), ratios.data_ptr(), MSDA._ptr(tok), out.data_ptr(), sink.data_ptr(),
+                  N, *bank, S, Lq, Hh, D, L, P, n, M, Lr, Nr, refuse_ok=True, what="mmfs_sample_forward"):
         return None
-    MSDA._check(rc, "mmfs_sample_forward")
     return out, sink

@@ -7,8 +7,6 @@ LLM path those "other" kernels were the largest cost (profiles/r02_module_bench_
 one storage type out of fp32 / fp16 / bf16, a row of whole 16-byte vectors, at most 8192 16-bit channels);
 otherwise the module evaluates the same mathematics with framework ops, which is what the CPU tests run.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -16,18 +14,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_rmsnorm_supported.restype = _int
-_lib.mmfs_rmsnorm_supported.argtypes = [_int, _i64]
-_lib.mmfs_rmsnorm_forward.restype = _int
-_lib.mmfs_rmsnorm_forward.argtypes = [_int, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp]
-_lib.mmfs_rmsnorm_backward.restype = _int
-_lib.mmfs_rmsnorm_backward.argtypes = [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]
-_lib.mmfs_rmsnorm_backward_partials.restype = _int
-_lib.mmfs_rmsnorm_backward_partials.argtypes = [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]
-_lib.mmfs_rmsnorm_backward_partials_rows.restype = _int
-_lib.mmfs_rmsnorm_backward_partials_rows.argtypes = [_i64]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 _ok = {}
 
 
@@ -49,11 +36,8 @@ def _rmsnorm_launch(x, weight, eps, keep):
     rows = xc.numel() // C if C else 0
     y = torch.empty_like(xc)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if keep else None
-    with MSDA._on_device(x.device):
-        rc = MSDA._launch("mmfs_rmsnorm_fwd", x.device, _lib.mmfs_rmsnorm_forward, _CODE[x.dtype], xc.data_ptr(),
-                          wc.data_ptr(), y.data_ptr(), rstd.data_ptr() if keep else None, rows, C, float(eps),
-                          MSDA._stream(x.device))
-    MSDA._check(rc, "mmfs_rmsnorm_forward")
+    MSDA._call("mmfs_rmsnorm_fwd", "mmfs_rmsnorm_forward", x.device, _CODE[x.dtype], xc.data_ptr(), wc.data_ptr(),
+               y.data_ptr(), MSDA._ptr(rstd), rows, C, float(eps))
     return y, xc, wc, rstd
 
 
@@ -87,9 +71,6 @@ class RMSNormFunction(Function):
         gx = torch.empty_like(xc)
         # every workgroup leaves its share of the gain gradient in a row of its own (no atomics), added up here
         parts = torch.empty((int(_lib.mmfs_rmsnorm_backward_partials_rows(rows)), C), dtype=torch.float32, device=xc.device)
-        with MSDA._on_device(xc.device):
-            rc = MSDA._launch("mmfs_rmsnorm_bwd", xc.device, _lib.mmfs_rmsnorm_backward_partials, _CODE[xc.dtype],
-                              gy.data_ptr(), xc.data_ptr(), wc.data_ptr(), rstd.data_ptr(), gx.data_ptr(), parts.data_ptr(),
-                              rows, C, MSDA._stream(xc.device))
-        MSDA._check(rc, "mmfs_rmsnorm_backward_partials")
+        MSDA._call("mmfs_rmsnorm_bwd", "mmfs_rmsnorm_backward_partials", xc.device, _CODE[xc.dtype], gy.data_ptr(),
+                   xc.data_ptr(), wc.data_ptr(), rstd.data_ptr(), gx.data_ptr(), parts.data_ptr(), rows, C)
         return gx, parts.sum(0).to(wc.dtype), None

@@ -7,8 +7,6 @@ per level -- and the bank builder's transposition back) as one or two gfx950 ker
 ``pyramid_head_supported`` tells the module whether the route applies; otherwise the module runs the reference's
 framework statement unchanged.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -16,14 +14,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_pyramid_head_supported.restype = _int
-_lib.mmfs_pyramid_head_supported.argtypes = [_int, _i64, _i64, _i64, _int]
-_lib.mmfs_pyramid_head_forward.restype = _int
-_lib.mmfs_pyramid_head_forward.argtypes = [_int] + [_vp] * 12 + [_i64] * 4 + [_int, _int, _vp]
-_lib.mmfs_pyramid_head_backward.restype = _int
-_lib.mmfs_pyramid_head_backward.argtypes = [_int] + [_vp] * 7 + [_i64] * 4 + [_int, _int, _vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 NCHW, NHWC = 0, 1
 
 # kernel calls since import, for tests and tools that ask which route the module took
@@ -76,9 +67,6 @@ def pyramid_head_supported(c, xs, c1, pos, H, W, mask):
     return True
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
 
 class PyramidHeadFunction(Function):
     """(c [B, 21 HW / 4, C], x1, x2, x3, x4 [B, HW, C], up [B, 4HW, 4C], c1 [B, C, 4H, 4W] contiguous or channels_last,
@@ -107,11 +95,8 @@ class PyramidHeadFunction(Function):
         tabs = [MSDA._aligned(pos[l].contiguous()) if pos is not None and on[l] else None for l in range(4)]
         S = sum(h * w for (h, w), o in zip(level_sizes(H, W), on) if o)
         out = torch.empty((B, S, C), dtype=dt, device=dev)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("pyramid_fwd", dev, _lib.mmfs_pyramid_head_forward, _CODE[dt], c.data_ptr(), *map(_ptr, xs),
-                              _ptr(up), _ptr(c1), *map(_ptr, tabs), out.data_ptr(), B, H, W, C, mask, layout,
-                              MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_pyramid_head_forward")
+        MSDA._call("pyramid_fwd", "mmfs_pyramid_head_forward", dev, _CODE[dt], c.data_ptr(), *map(MSDA._ptr, xs),
+                   MSDA._ptr(up), MSDA._ptr(c1), *map(MSDA._ptr, tabs), out.data_ptr(), B, H, W, C, mask, layout)
         launches["forward"] += 1
         ctx.conf = (B, H, W, C, mask, layout, c.shape[1], dt, dev)
         return out
@@ -131,10 +116,8 @@ class PyramidHeadFunction(Function):
             g_c1 = torch.empty((B, C, 4 * H, 4 * W), dtype=dt, device=dev,
                                memory_format=torch.channels_last if layout == NHWC else torch.contiguous_format)
         if B * C and any(t is not None for t in gx + [g_up, g_c1]):
-            with MSDA._on_device(dev):
-                rc = MSDA._launch("pyramid_bwd", dev, _lib.mmfs_pyramid_head_backward, _CODE[dt], g.data_ptr(), _ptr(g_up),
-                                  _ptr(g_c1), *map(_ptr, gx), B, H, W, C, mask, layout, MSDA._stream(dev))
-            MSDA._check(rc, "mmfs_pyramid_head_backward")
+            MSDA._call("pyramid_bwd", "mmfs_pyramid_head_backward", dev, _CODE[dt], g.data_ptr(), MSDA._ptr(g_up),
+                       MSDA._ptr(g_c1), *map(MSDA._ptr, gx), B, H, W, C, mask, layout)
             launches["backward"] += 1
         # the adapter tokens' gradient is levels 2..4 of g itself; a level that was not produced gives none (zeros)
         lo = 16 * H * W if on[0] else 0

@@ -6,8 +6,6 @@ from the device: every call can be captured into a graph.
 ``qk_attn_supported`` tells ``mmfs_amd.resampler`` whether the kernels apply; otherwise it states the same mathematics
 with framework ops.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -15,15 +13,6 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int, _f32 = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-if not hasattr(_lib, "mmfs_qk_attn_forward"):           # (additive at ABI 14: detected by symbol)
-    raise ImportError(f"{MSDA.library_path()} has no mmfs_qk_attn_forward: rebuild the library")
-_lib.mmfs_qk_attn_supported.restype = _int
-_lib.mmfs_qk_attn_supported.argtypes = [_int] + [_i64] * 3
-_lib.mmfs_qk_attn_forward.restype = _int
-_lib.mmfs_qk_attn_forward.argtypes = [_int] + [_vp] * 7 + [_int, _f32, _vp, _int, _i64] + [_vp] * 3 + [_i64] * 5 + [_vp]
-_lib.mmfs_qk_attn_backward.restype = _int
-_lib.mmfs_qk_attn_backward.argtypes = [_int] + [_vp] * 7 + [_int, _f32, _vp, _int, _i64] + [_vp] * 8 + [_i64] * 5 + [_vp]
 _CODE = MSDA._DTYPE_CODE
 HEAD_DIM = 64
 
@@ -74,9 +63,6 @@ def _bias(key_bias, dev, dt, B, Nk):
     return t, code, 0 if shared else Nk
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
 
 class QKNormAttentionFunction(Function):
     """(q, k, v, q_norm_weight, q_norm_bias, k_norm_weight, k_norm_bias, eps, key_bias, num_heads) -> (context, lse):
@@ -98,11 +84,9 @@ class QKNormAttentionFunction(Function):
         # one allocation: lse | (m, l)
         buf = torch.empty(3 * B * H * Nq, dtype=torch.float32, device=dev)
         lse, stats = buf.split((B * H * Nq, 2 * B * H * Nq))
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("qk_attn_fwd", dev, _lib.mmfs_qk_attn_forward, _CODE[dt], q.data_ptr(), k.data_ptr(),
-                              v.data_ptr(), *(_ptr(t) for t in norm), ncode, float(eps), _ptr(bias), bcode, bstride,
-                              out.data_ptr(), lse.data_ptr(), stats.data_ptr(), B, H, C // H, Nq, Nk, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_qk_attn_forward")
+        MSDA._call("qk_attn_fwd", "mmfs_qk_attn_forward", dev, _CODE[dt], q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                   *(MSDA._ptr(t) for t in norm), ncode, float(eps), MSDA._ptr(bias), bcode, bstride, out.data_ptr(),
+                   lse.data_ptr(), stats.data_ptr(), B, H, C // H, Nq, Nk)
         launches["forward"] += 1
         ctx.save_for_backward(q, k, v, out, stats, bias, *(t for t in norm if t is not None))
         ctx.conf = (B, H, Nq, Nk, C, float(eps), norm[0] is not None, key_bias is not None, ncode, bcode, bstride,
@@ -123,13 +107,10 @@ class QKNormAttentionFunction(Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         partials = torch.empty((B * H, 4, HEAD_DIM), dtype=torch.float32, device=dev) if has_norm else None
         dparams = torch.empty((4, HEAD_DIM), dtype=torch.float32, device=dev) if has_norm else None
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("qk_attn_bwd", dev, _lib.mmfs_qk_attn_backward, _CODE[dt], q.data_ptr(), k.data_ptr(),
-                              v.data_ptr(), *(_ptr(t) for t in norm), ncode, eps, _ptr(bias), bcode, bstride, out.data_ptr(),
-                              g.data_ptr(),
-                              stats.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _ptr(partials),
-                              _ptr(dparams), B, H, C // H, Nq, Nk, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_qk_attn_backward")
+        MSDA._call("qk_attn_bwd", "mmfs_qk_attn_backward", dev, _CODE[dt], q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                   *(MSDA._ptr(t) for t in norm), ncode, eps, MSDA._ptr(bias), bcode, bstride, out.data_ptr(), g.data_ptr(),
+                   stats.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), MSDA._ptr(partials), MSDA._ptr(dparams), B,
+                   H, C // H, Nq, Nk)
         launches["backward"] += 2 if has_norm else 1
         gp = [None] * 4
         if has_norm:

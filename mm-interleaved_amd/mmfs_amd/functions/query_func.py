@@ -12,8 +12,6 @@ checkpointing) and evaluate the backward with the framework's own LayerNorm back
 returned.  Anything the kernels do not take (fp32 storage, CPU tensors: what the CPU tests run) stays on the framework's
 kernels in ``MMFSBlock``.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -21,14 +19,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_query_prep_supported.restype = _int
-_lib.mmfs_query_prep_supported.argtypes = [_int, _i64, _i64]
-_lib.mmfs_query_prep.restype = _int
-_lib.mmfs_query_prep.argtypes = [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp]
-_lib.mmfs_tokens_add.restype = _int
-_lib.mmfs_tokens_add.argtypes = [_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp]
-_CODE = {torch.float16: 1, torch.bfloat16: 2}
+_CODE = {t: MSDA._DTYPE_CODE[t] for t in (torch.float16, torch.bfloat16)}       # the types served: 16-bit storage only
 _ok = {}
 
 
@@ -54,12 +45,8 @@ def query_prep(sample, weight, bias, eps, pos=None, stats=False):
     q = torch.empty((B, H * W, C), dtype=x.dtype, device=x.device)
     mean = torch.empty((B, H * W, 1), dtype=torch.float32, device=x.device) if stats else None
     rstd = torch.empty_like(mean) if stats else None
-    with MSDA._on_device(x.device):
-        rc = MSDA._launch("mmfs_query_prep", x.device, _lib.mmfs_query_prep, _CODE[x.dtype], x.data_ptr(), g.data_ptr(),
-                          b.data_ptr(), p.data_ptr() if p is not None else None, q.data_ptr(),
-                          mean.data_ptr() if stats else None, rstd.data_ptr() if stats else None,
-                          B, C, H * W, float(eps), MSDA._stream(x.device))
-    MSDA._check(rc, "mmfs_query_prep")
+    MSDA._call("mmfs_query_prep", "mmfs_query_prep", x.device, _CODE[x.dtype], x.data_ptr(), g.data_ptr(), b.data_ptr(),
+               MSDA._ptr(p), q.data_ptr(), MSDA._ptr(mean), MSDA._ptr(rstd), B, C, H * W, float(eps))
     return (q, mean, rstd) if stats else q
 
 
@@ -95,10 +82,8 @@ def tokens_add(tokens, residual):
     t = MSDA._aligned(tokens.contiguous())
     r = MSDA._aligned(residual.contiguous())
     y = torch.empty_like(r)
-    with MSDA._on_device(r.device):
-        rc = MSDA._launch("mmfs_tokens_add", r.device, _lib.mmfs_tokens_add, _CODE[r.dtype], t.data_ptr(), r.data_ptr(),
-                          y.data_ptr(), B, C, H * W, MSDA._stream(r.device))
-    MSDA._check(rc, "mmfs_tokens_add")
+    MSDA._call("mmfs_tokens_add", "mmfs_tokens_add", r.device, _CODE[r.dtype], t.data_ptr(), r.data_ptr(), y.data_ptr(), B,
+               C, H * W)
     return y
 
 

@@ -7,8 +7,6 @@ the device: every call can be captured into a graph.
 ``sequence_supported`` tells ``mmfs_amd.sequence`` whether the kernels apply; otherwise it states the same mathematics
 with framework ops.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -16,22 +14,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-_lib.mmfs_sequence_supported.restype = _int
-_lib.mmfs_sequence_supported.argtypes = [_int, _i64]
-_lib.mmfs_sequence_index.restype = _int
-_lib.mmfs_sequence_index.argtypes = [_vp] + [_i64] * 6 + [_vp] * 7
-_lib.mmfs_sequence_embed_forward.restype = _int
-_lib.mmfs_sequence_embed_forward.argtypes = [_int, _int] + [_vp] * 4 + [_i64, _vp, _vp] + [_i64] * 3 + [_vp]
-_lib.mmfs_sequence_embed_backward.restype = _int
-_lib.mmfs_sequence_embed_backward.argtypes = [_int, _int] + [_vp] * 9 + [_i64] * 5 + [_vp]
-_lib.mmfs_sequence_context_forward.restype = _int
-_lib.mmfs_sequence_context_forward.argtypes = [_int] + [_vp] * 9 + [_i64] * 6 + [_vp]
-_lib.mmfs_sequence_context_backward_workspace_bytes.restype = _i64
-_lib.mmfs_sequence_context_backward_workspace_bytes.argtypes = [_int, _i64, _i64]
-_lib.mmfs_sequence_context_backward.restype = _int
-_lib.mmfs_sequence_context_backward.argtypes = [_int] + [_vp] * 9 + [_i64] * 6 + [_vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 MAX_TOKENS = 1 << 22
 
 # kernel calls since import, for tests and tools that ask which route the module took
@@ -50,9 +33,6 @@ def sequence_supported(ref, *others, C=None):
     return all(t is None or (t.device == ref.device and t.dtype == ref.dtype) for t in others)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
 
 def sequence_index(text_ids, image_token_id, soi_token_id, n_vis, n_images):
     """text_ids [B, L] (long, on the device) -> (img_rank [B L], img_pos [n_vis], soi_row [n_images], soi_col [n_images],
@@ -66,10 +46,8 @@ def sequence_index(text_ids, image_token_id, soi_token_id, n_vis, n_images):
     sizes = (B * L, n_vis, n_images, n_images, B + 1, 2)
     buf = torch.empty(sum(sizes), dtype=torch.int32, device=dev)
     parts = buf.split(sizes)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("seq_index", dev, _lib.mmfs_sequence_index, ids.data_ptr(), B, L, int(image_token_id),
-                          int(soi_token_id), n_vis, n_images, *[p.data_ptr() for p in parts], MSDA._stream(dev))
-    MSDA._check(rc, "mmfs_sequence_index")
+    MSDA._call("seq_index", "mmfs_sequence_index", dev, ids.data_ptr(), B, L, int(image_token_id), int(soi_token_id), n_vis,
+               n_images, *[p.data_ptr() for p in parts])
     launches["index"] += 1
     return parts
 
@@ -90,11 +68,9 @@ class SequenceEmbedFunction(Function):
         soi_c = MSDA._aligned(soi_token.contiguous())
         ids = text_ids.contiguous()
         out = torch.empty((B, L, C), dtype=dt, device=dev)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("seq_embed_fwd", dev, _lib.mmfs_sequence_embed_forward, _CODE[dt], _CODE[text.dtype],
-                              text_c.data_ptr(), vis_c.data_ptr(), soi_c.data_ptr(), ids.data_ptr(), int(soi_token_id),
-                              img_rank.data_ptr(), out.data_ptr(), B * L, C, n_vis, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_sequence_embed_forward")
+        MSDA._call("seq_embed_fwd", "mmfs_sequence_embed_forward", dev, _CODE[dt], _CODE[text.dtype], text_c.data_ptr(),
+                   vis_c.data_ptr(), soi_c.data_ptr(), ids.data_ptr(), int(soi_token_id), img_rank.data_ptr(),
+                   out.data_ptr(), B * L, C, n_vis)
         launches["embed_forward"] += 1
         ctx.save_for_backward(img_rank, img_pos, soi_row, soi_col, counts)
         ctx.conf = (B, L, C, n_vis, n_images, dt, text.dtype, dev, tuple(soi_token.shape))
@@ -111,12 +87,9 @@ class SequenceEmbedFunction(Function):
         g_vis = torch.empty((n_vis, C), dtype=dt, device=dev) if need[1] else None
         g_soi = torch.empty(soi_shape, dtype=dt, device=dev) if need[2] else None
         if any(t is not None and t.numel() for t in (g_text, g_vis, g_soi)):
-            with MSDA._on_device(dev):
-                rc = MSDA._launch("seq_embed_bwd", dev, _lib.mmfs_sequence_embed_backward, _CODE[dt], _CODE[text_dt],
-                                  g.data_ptr(), img_rank.data_ptr(), img_pos.data_ptr(), soi_row.data_ptr(),
-                                  soi_col.data_ptr(), counts.data_ptr(), _ptr(g_text), _ptr(g_vis), _ptr(g_soi), B * L, L, C,
-                                  n_vis, n_images, MSDA._stream(dev))
-            MSDA._check(rc, "mmfs_sequence_embed_backward")
+            MSDA._call("seq_embed_bwd", "mmfs_sequence_embed_backward", dev, _CODE[dt], _CODE[text_dt], g.data_ptr(),
+                       img_rank.data_ptr(), img_pos.data_ptr(), soi_row.data_ptr(), soi_col.data_ptr(), counts.data_ptr(),
+                       MSDA._ptr(g_text), MSDA._ptr(g_vis), MSDA._ptr(g_soi), B * L, L, C, n_vis, n_images)
             launches["embed_backward"] += 1
         return (g_text, g_vis, g_soi) + (None,) * 8
 
@@ -140,11 +113,9 @@ class ContextGatherFunction(Function):
         bos_c = None if bos_idx is None else bos_idx.contiguous()
         out = torch.empty((n_images, max_len, C), dtype=dt, device=dev)
         mask = torch.empty((n_images, max_len), dtype=torch.long, device=dev)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("seq_context_fwd", dev, _lib.mmfs_sequence_context_forward, _CODE[dt], src_c.data_ptr(),
-                              _ptr(pad_c), _ptr(pos_c), soi_row.data_ptr(), soi_col.data_ptr(), _ptr(start_c), _ptr(bos_c),
-                              out.data_ptr(), mask.data_ptr(), B, L, C, n_images, max_len, seq_len, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_sequence_context_forward")
+        MSDA._call("seq_context_fwd", "mmfs_sequence_context_forward", dev, _CODE[dt], src_c.data_ptr(), MSDA._ptr(pad_c),
+                   MSDA._ptr(pos_c), soi_row.data_ptr(), soi_col.data_ptr(), MSDA._ptr(start_c), MSDA._ptr(bos_c),
+                   out.data_ptr(), mask.data_ptr(), B, L, C, n_images, max_len, seq_len)
         launches["context_forward"] += 1
         ctx.save_for_backward(soi_row, soi_col, row_first, start_c, bos_c)
         ctx.conf = (B, L, C, n_images, max_len, seq_len, dt, dev, pad_row is not None)
@@ -166,10 +137,8 @@ class ContextGatherFunction(Function):
             MSDA._check(min(nbytes, 0), "mmfs_sequence_context_backward_workspace_bytes")
             ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
         if g_src is not None or g_pad is not None:
-            with MSDA._on_device(dev):
-                rc = MSDA._launch("seq_context_bwd", dev, _lib.mmfs_sequence_context_backward, _CODE[dt], g.data_ptr(),
-                                  soi_row.data_ptr(), soi_col.data_ptr(), row_first.data_ptr(), _ptr(start_c), _ptr(bos_c),
-                                  _ptr(g_src), _ptr(g_pad), _ptr(ws), B, L, C, n_images, max_len, seq_len, MSDA._stream(dev))
-            MSDA._check(rc, "mmfs_sequence_context_backward")
+            MSDA._call("seq_context_bwd", "mmfs_sequence_context_backward", dev, _CODE[dt], g.data_ptr(), soi_row.data_ptr(),
+                       soi_col.data_ptr(), row_first.data_ptr(), MSDA._ptr(start_c), MSDA._ptr(bos_c), MSDA._ptr(g_src),
+                       MSDA._ptr(g_pad), MSDA._ptr(ws), B, L, C, n_images, max_len, seq_len)
             launches["context_backward"] += 1
         return (g_src, g_pad) + (None,) * 8

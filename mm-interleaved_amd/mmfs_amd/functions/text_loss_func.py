@@ -6,8 +6,6 @@ captured into a graph.
 ``text_loss_supported`` tells ``mmfs_amd.text_loss`` whether the kernels apply; otherwise it states the same mathematics
 with framework ops.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -15,16 +13,7 @@ from torch.autograd.function import once_differentiable
 import MultiScaleDeformableAttention as MSDA
 
 _lib = MSDA._lib
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-if not hasattr(_lib, "mmfs_text_loss_forward"):         # (additive at ABI 14: detected by symbol)
-    raise ImportError(f"{MSDA.library_path()} has no mmfs_text_loss_forward: rebuild the library")
-_lib.mmfs_text_loss_supported.restype = _int
-_lib.mmfs_text_loss_supported.argtypes = [_int, _i64]
-_lib.mmfs_text_loss_forward.restype = _int
-_lib.mmfs_text_loss_forward.argtypes = [_int] + [_vp] * 6 + [_i64] * 6 + [_int, _vp]
-_lib.mmfs_text_loss_backward.restype = _int
-_lib.mmfs_text_loss_backward.argtypes = [_int] + [_vp] * 6 + [_i64] * 6 + [_int, _vp]
-_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_CODE = MSDA._FLOAT_CODE
 REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 MAX_ROWS = 1 << 22
 
@@ -53,11 +42,8 @@ def _forward(logits, labels, first, ignore_index, code):
     buf = torch.empty(2 * B * n + 1, dtype=torch.float32, device=dev)
     loss, lse, out = buf.split((B * n, B * n, 1))
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    with MSDA._on_device(dev):
-        rc = MSDA._launch("text_loss_fwd", dev, _lib.mmfs_text_loss_forward, _CODE[dt], x.data_ptr(), lab.data_ptr(),
-                          loss.data_ptr(), lse.data_ptr(), out.data_ptr(), counts.data_ptr(), B, L, V, first, n,
-                          ignore_index, code, MSDA._stream(dev))
-    MSDA._check(rc, "mmfs_text_loss_forward")
+    MSDA._call("text_loss_fwd", "mmfs_text_loss_forward", dev, _CODE[dt], x.data_ptr(), lab.data_ptr(), loss.data_ptr(),
+               lse.data_ptr(), out.data_ptr(), counts.data_ptr(), B, L, V, first, n, ignore_index, code)
     launches["forward"] += 1
     return x, lab, loss.view(B, n), lse.view(B, n), out.view(()), counts
 
@@ -93,10 +79,7 @@ class TextLossFunction(Function):
             return (None,) * 5
         g = g.to(torch.float32).contiguous()
         grad = torch.empty((B, L, V), dtype=dt, device=dev)
-        with MSDA._on_device(dev):
-            rc = MSDA._launch("text_loss_bwd", dev, _lib.mmfs_text_loss_backward, _CODE[dt], x.data_ptr(), lab.data_ptr(),
-                              lse.data_ptr(), g.data_ptr(), counts.data_ptr(), grad.data_ptr(), B, L, V, first, n,
-                              ignore_index, code, MSDA._stream(dev))
-        MSDA._check(rc, "mmfs_text_loss_backward")
+        MSDA._call("text_loss_bwd", "mmfs_text_loss_backward", dev, _CODE[dt], x.data_ptr(), lab.data_ptr(), lse.data_ptr(),
+                   g.data_ptr(), counts.data_ptr(), grad.data_ptr(), B, L, V, first, n, ignore_index, code)
         launches["backward"] += 1
         return (grad,) + (None,) * 4

@@ -6,6 +6,17 @@ import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mm-interleaved_amd")
+LIB = os.path.join(PKG, "libmmfs_msda.so")
+
+
+def bound_library():
+    """A ``ctypes.CDLL`` handle of the caller's own on the kernel library, every entry point of include/mmfs_msda.h bound
+    by the package's one signature table (mmfs_abi.py)."""
+    import ctypes
+    import mmfs_abi                                        # (beside the shim; conftest.py puts that directory on sys.path)
+    assert os.path.exists(LIB), "run __graft_entry__.build() / make -C mm-interleaved_amd/csrc"
+    return mmfs_abi.bind(ctypes.CDLL(LIB))
 
 
 def load_golden(name):

@@ -9,6 +9,8 @@ import re
 import pytest
 import torch
 
+from helpers import bound_library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
 LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
@@ -35,26 +37,43 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(LIB)
     for n in declared_functions():
         assert hasattr(lib, n), f"{n} declared in include/mmfs_msda.h but not exported"
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     want = int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1))
     assert lib.mmfs_msda_abi_version() == want
 
 
+def header_prototypes():
+    """[(name, return kind, argument kinds)] of every ``type mmfs_name(args);`` of the header, in its order.  Kinds as in
+    mmfs_abi.py: i int, l int64_t, u unsigned, f float, p whatever has a ``*``; returns also s ``const char *`` and v void."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
+    kinds = {"int": "i", "int64_t": "l", "unsigned": "u", "float": "f", "const char *": "s", "void": "v"}
+    out = []
+    for ret, name, args in re.findall(r"^(const char \*|\w+)\s*\b(mmfs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        args = [" ".join(a.split()) for a in args.split(",")]
+        out.append((name, kinds[ret], "".join("p" if "*" in a else kinds[a.rsplit(" ", 1)[0]] for a in args if a != "void")))
+    return out
+
+
+def test_signature_table_is_the_header():
+    """mmfs_abi.SIGNATURES -- what every Python caller's ctypes signatures come from -- against the prototypes of
+    include/mmfs_msda.h: the same names in the same order, the same return kind, the same kind at every argument
+    position.  Every ``mmfs_*(`` name of the header must have been read as a prototype."""
+    import mmfs_abi
+    protos = header_prototypes()
+    assert len(protos) == len(declared_functions()), sorted(set(declared_functions()) - {p[0] for p in protos})
+    table = mmfs_abi.SIGNATURES
+    assert list(table) == [p[0] for p in protos]
+    for name, ret, args in protos:
+        assert table[name] == (ret, args), f"{name}: the table says {table[name]}, the header {(ret, args)}"
+
+
 def test_argument_errors_do_not_need_a_gpu():
-    lib = ctypes.CDLL(LIB)
-    i64, vp = ctypes.c_int64, ctypes.c_void_p
-    lib.mmfs_msda_forward.restype = ctypes.c_int
-    lib.mmfs_msda_forward.argtypes = [ctypes.c_int] + [vp] * 6 + [i64] * 7 + [vp]
-    lib.mmfs_msda_status_string.restype = ctypes.c_char_p
-    lib.mmfs_msda_status_string.argtypes = [ctypes.c_int]
+    lib = bound_library()
     null = [None] * 6
     assert lib.mmfs_msda_forward(9, *null, 1, 1, 1, 1, 1, 1, 1, None) == -1       # dtype
     assert lib.mmfs_msda_forward(0, *null, -1, 1, 1, 1, 1, 1, 1, None) == -2      # dims
     assert lib.mmfs_msda_forward(0, *null, 1, 1, 1, 1, 1, 1, 1, None) == -3       # null
     assert lib.mmfs_msda_forward(0, *null, 0, 1, 1, 1, 1, 1, 1, None) == 0        # empty batch
     # the LDS-resident formulation exists for 16-bit storage and heads of 64 / 128 channels only
-    lib.mmfs_msda_forward_flags.restype = ctypes.c_int
-    lib.mmfs_msda_forward_flags.argtypes = [ctypes.c_int] + [vp] * 6 + [i64] * 7 + [ctypes.c_uint, vp]
     fake = [ctypes.c_void_p(4096)] * 6                                             # aligned, never dereferenced
     assert lib.mmfs_msda_forward_flags(0, *fake, 1, 64, 1, 128, 1, 1, 1, 2, None) == -5     # fp32
     assert lib.mmfs_msda_forward_flags(2, *fake, 1, 64, 1, 32, 1, 1, 1, 2, None) == -5      # D = 32
@@ -65,11 +84,8 @@ def test_argument_errors_do_not_need_a_gpu():
 
 def test_bank_entry_points_validate_on_the_host():
     """mmfs_bank_gather / mmfs_bank_scatter: argument errors and empty problems return before any launch."""
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    for f in (lib.mmfs_bank_gather, lib.mmfs_bank_scatter):
-        f.restype = ci
-        f.argtypes = [ci, ci, vp, vp, vp, vp, i64, i64, i64, vp]
+    lib = bound_library()
+    i64, vp = ctypes.c_int64, ctypes.c_void_p
     ptrs = (vp * 2)(0x1000, 0x2000)                   # never dereferenced on these paths
     hw = (i64 * 2)(64, 16)
     P, H = ctypes.cast(ptrs, vp), ctypes.cast(hw, vp)
@@ -107,11 +123,7 @@ def test_autograd_function_surface():
 
 
 def test_backward_workspace_query_is_host_only():
-    lib = ctypes.CDLL(LIB)
-    i64 = ctypes.c_int64
-    f = lib.mmfs_msda_backward_workspace_bytes
-    f.restype = i64
-    f.argtypes = [ctypes.c_int] + [i64] * 7 + [ctypes.c_uint]
+    f = bound_library().mmfs_msda_backward_workspace_bytes
     dims = (8, 5440, 8, 128, 4, 4096, 4)
     pts = 8 * 4096 * 8 * 4 * 4
     # bf16, canonical levels: re-packed loc/attn + level cursors + plan + per-pixel / per-cell run
@@ -163,14 +175,8 @@ def test_hybrid_workspace_queries_are_host_only():
     cores when the caller hands over a HOST copy of the level table; its workspace query computes on
     the host."""
     import numpy as np
-    lib = ctypes.CDLL(LIB)
-    i64, vp = ctypes.c_int64, ctypes.c_void_p
-    bw = lib.mmfs_msda_backward_hybrid_workspace_bytes
-    bw.restype = i64
-    bw.argtypes = [ctypes.c_int, vp, vp] + [i64] * 7 + [ctypes.c_uint]
-    plain = lib.mmfs_msda_backward_workspace_bytes
-    plain.restype = i64
-    plain.argtypes = [ctypes.c_int] + [i64] * 7 + [ctypes.c_uint]
+    lib = bound_library()
+    bw, plain = lib.mmfs_msda_backward_hybrid_workspace_bytes, lib.mmfs_msda_backward_workspace_bytes
     sh = np.array([[64, 64], [32, 32], [16, 16], [8, 8]], dtype=np.int64)
     st = np.array([0, 4096, 5120, 5376], dtype=np.int64)
     dims = (8, 5440, 8, 128, 4, 4096, 4)
@@ -189,11 +195,7 @@ def test_hybrid_workspace_queries_are_host_only():
 def test_sample_forward_argument_errors_return_before_any_launch():
     """mmfs_sample_forward (plan -> sampler in one kernel): dtype / dims / unsupported shapes / NULL pointers are
     answered on the host."""
-    lib = ctypes.CDLL(LIB)
-    i64, vp = ctypes.c_int64, ctypes.c_void_p
-    f = lib.mmfs_sample_forward
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_int] + [vp] * 12 + [i64] * 11 + [vp]
+    f = bound_library().mmfs_sample_forward
     null = [None] * 12
     #            N  S     Lq  H  D   L  P  n  M  Lr Nr
     dims = [2, 1344, 16, 16, 64, 3, 8, 1, 8, 1, 1]
@@ -215,10 +217,7 @@ def test_environment_knobs_are_one_table():
             continue
         text = open(path).read()
         assert "getenv(" not in text, path
-    lib = ctypes.CDLL(LIB)
-    lib.mmfs_env_knob.restype = ctypes.c_int
-    lib.mmfs_env_knob.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_char_p)] * 3
-    lib.mmfs_env_reload.restype = None
+    lib = bound_library()
     names, i = [], 0
     name, doc, val = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_char_p()
     while lib.mmfs_env_knob(i, ctypes.byref(name), ctypes.byref(doc), ctypes.byref(val)) == 0:

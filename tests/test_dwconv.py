@@ -10,23 +10,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_dwconv_tokens_supported", "mmfs_dwconv_tokens_forward", "mmfs_dwconv_tokens_backward_workspace_bytes",
          "mmfs_dwconv_tokens_backward")
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_dwconv_tokens_supported.restype = ci
-    lib.mmfs_dwconv_tokens_supported.argtypes = [ci, i64, i64, ci]
-    lib.mmfs_dwconv_tokens_forward.restype = ci
-    lib.mmfs_dwconv_tokens_forward.argtypes = [ci] + [vp] * 6 + [i64] * 4 + [ci, vp]
-    lib.mmfs_dwconv_tokens_backward_workspace_bytes.restype = i64
-    lib.mmfs_dwconv_tokens_backward_workspace_bytes.argtypes = [ci, vp] + [i64] * 4 + [ci]
-    lib.mmfs_dwconv_tokens_backward.restype = ci
-    lib.mmfs_dwconv_tokens_backward.argtypes = [ci] + [vp] * 9 + [i64] * 4 + [ci, vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -36,7 +24,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
     assert "mmfs_dwconv_tokens_supported" in raw[raw.index("#define MMFS_MSDA_ABI_VERSION"):raw.index("enum mmfs_dtype")]

@@ -1,7 +1,6 @@
 """CPU-side checks of the inference-only fp8 value bank (include/mmfs_msda.h "fp8 bank"): the C ABI declares and exports its
 three entries at ABI 14, refuses bad arguments before any launch (null pointers throughout: nothing reaches a device), and
 the torch statement of the quantiser rule behaves as documented on its edge cases."""
-import ctypes
 import os
 import re
 import sys
@@ -12,23 +11,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mm-interleaved_amd")]
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 E_DTYPE, E_DIMS, E_NULLPTR, E_UNSUPPORTED = -1, -2, -3, -5
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 ENTRIES = ("mmfs_bank_quantize_fp8", "mmfs_msda_forward_fp8", "mmfs_sample_forward_heads_fp8")
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    lib.mmfs_bank_quantize_fp8.restype = _int
-    lib.mmfs_bank_quantize_fp8.argtypes = [_int, _vp] + [_i64] * 4 + [_vp, _vp, _vp]
-    lib.mmfs_msda_forward_fp8.restype = _int
-    lib.mmfs_msda_forward_fp8.argtypes = [_int] + [_vp] * 7 + [_i64] * 2 + [_int] + [_i64] * 6 + [_vp]
-    lib.mmfs_sample_forward_heads_fp8.restype = _int
-    lib.mmfs_sample_forward_heads_fp8.argtypes = ([_int] + [_vp] * 6 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
-                                                  + [_i64] * 10 + [_vp])
-    lib.mmfs_msda_abi_version.restype = _int
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_header_declares_and_library_exports_the_fp8_entries_at_abi_14():
@@ -86,8 +73,6 @@ def test_sampler_fp8_refuses_bad_arguments_before_any_launch():
 
 def test_existing_entries_still_refuse_other_dtypes():
     lib = _lib()
-    lib.mmfs_msda_forward_shared.restype = _int
-    lib.mmfs_msda_forward_shared.argtypes = [_int] + [_vp] * 6 + [_i64] * 2 + [_int] + [_i64] * 6 + [ctypes.c_uint, _vp]
     assert lib.mmfs_msda_forward_shared(4, None, None, None, None, None, None, 8, 8, 0, 64, 8, 128, 4, 16, 4, 0, None) == E_DTYPE
 
 

@@ -18,7 +18,6 @@ import front_end_refs as R
 from front_end_refs import worst
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
 
 
@@ -288,30 +287,7 @@ def test_linear_bound_passes_fp32_sums_and_fails_a_dropped_piece(dtype):
 OK, E_DTYPE, E_DIMS, E_NULL, E_ALIGN, E_UNSUP = 0, -1, -2, -3, -4, -5
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci, cf = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    sig = {
-        "mmfs_plan_forward": [ci] + [vp] * 11 + [i64] * 9 + [vp],
-        "mmfs_plan_forward_heads": [ci, vp, vp, i64, i64, vp, vp, i64, i64] + [vp] * 7 + [i64] * 9 + [vp],
-        "mmfs_plan_backward": [ci] + [vp] * 12 + [i64] * 9 + [vp],
-        "mmfs_plan_backward_heads": [ci] + [vp] * 8 + [vp, vp, i64, i64, ci, vp, vp, i64, i64] + [i64] * 9 + [vp],
-        "mmfs_rmsnorm_supported": [ci, i64],
-        "mmfs_rmsnorm_forward": [ci, vp, vp, vp, vp, i64, i64, cf, vp],
-        "mmfs_rmsnorm_backward": [ci] + [vp] * 6 + [i64, i64, vp],
-        "mmfs_rmsnorm_backward_partials": [ci] + [vp] * 6 + [i64, i64, vp],
-        "mmfs_rmsnorm_backward_partials_rows": [i64],
-        "mmfs_query_prep_supported": [ci, i64, i64],
-        "mmfs_query_prep": [ci] + [vp] * 7 + [i64] * 3 + [cf, vp],
-        "mmfs_tokens_add": [ci, vp, vp, vp, i64, i64, i64, vp],
-        "mmfs_linear_small_supported": [ci, i64, i64, i64],
-        "mmfs_linear_small": [ci] + [vp] * 4 + [i64] * 5 + [vp],
-        "mmfs_linear_small_add": [ci] + [vp] * 5 + [i64] * 6 + [vp],
-    }
-    for n, a in sig.items():
-        getattr(lib, n).restype = ci
-        getattr(lib, n).argtypes = a
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def in_a_child_without_devices(check):

@@ -23,8 +23,8 @@ CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def lib():
-    from mmfs_amd.functions import linear_func, mmfs_plan_func, norm_func, query_func  # noqa: F401  (argtypes)
-    return mmfs_plan_func._lib
+    import MultiScaleDeformableAttention as MSDA
+    return MSDA._lib
 
 
 def stream():

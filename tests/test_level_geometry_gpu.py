@@ -89,7 +89,7 @@ BWD_ROUTES = [
     ("taps=gather", dict(register=True, taps="gather"), ("hybrid+gather", "sequence+gather")),
     ("taps=lds", dict(register=True, taps="lds"), ("hybrid+lds", "sequence+lds")),
 ]
-# flags arguments of the entry points (MultiScaleDeformableAttention.py argtypes): their position in the call
+# flags arguments of the entry points (include/mmfs_msda.h): their position in the call
 _FLAG_ARG = {"mmfs_msda_backward_sorted": 20, "mmfs_msda_backward_hybrid": 21, "mmfs_msda_backward_checked": 19}
 _ENTRIES = tuple(_FLAG_ARG) + ("mmfs_msda_backward_taps",)
 

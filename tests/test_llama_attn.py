@@ -21,7 +21,6 @@ from mmfs_amd.llama_attn import LlamaKVCache, LlamaKVLayer, LlamaSelfAttention
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_llama_attn_supported", "mmfs_llama_attn_rope_append", "mmfs_llama_attn_decode_keys",
          "mmfs_llama_attn_decode_workspace_bytes", "mmfs_llama_attn_decode")
 CASES = ("prefill_decode", "all_masked_row", "decode_beams")
@@ -280,20 +279,7 @@ def test_routing_reasons_and_forced_routes():
 
 
 # ------------------------------------------------------------------ the C ABI without a GPU
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_llama_attn_supported.restype = ci
-    lib.mmfs_llama_attn_supported.argtypes = [ci] + [i64] * 3
-    lib.mmfs_llama_attn_rope_append.restype = ci
-    lib.mmfs_llama_attn_rope_append.argtypes = [ci] + [vp] * 6 + [i64] + [vp] * 5 + [i64] * 5 + [vp]
-    lib.mmfs_llama_attn_decode_keys.restype = i64
-    lib.mmfs_llama_attn_decode_keys.argtypes = [ci]
-    lib.mmfs_llama_attn_decode_workspace_bytes.restype = i64
-    lib.mmfs_llama_attn_decode_workspace_bytes.argtypes = [i64] * 3
-    lib.mmfs_llama_attn_decode.restype = ci
-    lib.mmfs_llama_attn_decode.argtypes = [ci] + [vp] * 6 + [ci, i64, i64] + [vp] * 2 + [i64] * 5 + [vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -303,7 +289,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
     assert "mmfs_llama_attn_supported" in raw[raw.index("#define MMFS_MSDA_ABI_VERSION"):raw.index("enum mmfs_dtype")]

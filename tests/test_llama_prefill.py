@@ -18,19 +18,11 @@ from mmfs_amd import llama_attn
 from mmfs_amd.llama_attn import LlamaSelfAttention
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 DTYPE, DIMS, NULLPTR, ALIGN, UNSUPPORTED = -1, -2, -3, -4, -5
 CAUSAL, VISIT_ALL = 1, 2
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_llama_attn_prefill.restype = ci
-    lib.mmfs_llama_attn_prefill.argtypes = [ci] + [vp] * 6 + [ci, i64, i64, i64, ctypes.c_uint, vp] + [i64] * 5 + [vp]
-    lib.mmfs_llama_attn_prefill_tiles.restype = i64
-    lib.mmfs_llama_attn_prefill_tiles.argtypes = [ci]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_the_tile_sizes_are_positive_and_the_package_reads_them_from_the_library():

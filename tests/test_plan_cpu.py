@@ -4,24 +4,16 @@ the sort tiles cover each cell exactly once within the LDS counters' capacity, a
 matrix-core reduce is planned exactly once -- by the one sort tile that holds its five cell rows or, on a seam
 between two tiles, by the slice's last workgroup.  (The GPU side of the same rules:
 tests/test_op_gpu.py::test_cell_sort_routes_match_oracle.)"""
-import ctypes
 import itertools
-import os
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
+from helpers import bound_library
 
 
 @pytest.fixture(scope="module")
 def selfcheck():
-    assert os.path.exists(LIB), "run __graft_entry__.build() / make -C mm-interleaved_amd/csrc"
-    lib = ctypes.CDLL(LIB)
-    fn = lib.mmfs_msda_plan_selfcheck
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
-    return fn
+    return bound_library().mmfs_msda_plan_selfcheck
 
 
 def test_levels_of_the_reference_configs(selfcheck):

@@ -13,21 +13,11 @@ from test_vit_adapter import T, load_fixture, rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_pyramid_head_supported", "mmfs_pyramid_head_forward", "mmfs_pyramid_head_backward")
 MASKS = [(0, 1, 2, 3), (1, 2, 3), (2,), (0, 3)]
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_pyramid_head_supported.restype = ci
-    lib.mmfs_pyramid_head_supported.argtypes = [ci, i64, i64, i64, ci]
-    lib.mmfs_pyramid_head_forward.restype = ci
-    lib.mmfs_pyramid_head_forward.argtypes = [ci] + [vp] * 12 + [i64] * 4 + [ci, ci, vp]
-    lib.mmfs_pyramid_head_backward.restype = ci
-    lib.mmfs_pyramid_head_backward.argtypes = [ci] + [vp] * 7 + [i64] * 4 + [ci, ci, vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 # ------------------------------------------------------------------ the formulas, restated in fp64
@@ -143,7 +133,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
 

@@ -21,7 +21,6 @@ from mmfs_amd.resampler import QKNormAttention
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_qk_attn_supported", "mmfs_qk_attn_forward", "mmfs_qk_attn_backward")
 CASES = ("self_qknorm", "cross_qknorm_masked", "cross_plain_77", "cross_one_key_left")
 BAR = 1e-12
@@ -228,16 +227,7 @@ def test_a_forced_kernel_route_that_does_not_apply_is_an_error_and_the_names_are
 
 
 # ------------------------------------------------------------------ the C ABI without a GPU
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci, cf = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.mmfs_qk_attn_supported.restype = ci
-    lib.mmfs_qk_attn_supported.argtypes = [ci] + [i64] * 3
-    lib.mmfs_qk_attn_forward.restype = ci
-    lib.mmfs_qk_attn_forward.argtypes = [ci] + [vp] * 7 + [ci, cf, vp, ci, i64] + [vp] * 3 + [i64] * 5 + [vp]
-    lib.mmfs_qk_attn_backward.restype = ci
-    lib.mmfs_qk_attn_backward.argtypes = [ci] + [vp] * 7 + [ci, cf, vp, ci, i64] + [vp] * 8 + [i64] * 5 + [vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -247,7 +237,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
     assert "mmfs_qk_attn_supported" in raw[raw.index("#define MMFS_MSDA_ABI_VERSION"):raw.index("enum mmfs_dtype")]

@@ -18,7 +18,6 @@ from mmfs_amd import sequence as seq
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_sequence_supported", "mmfs_sequence_index", "mmfs_sequence_embed_forward", "mmfs_sequence_embed_backward",
          "mmfs_sequence_context_forward", "mmfs_sequence_context_backward", "mmfs_sequence_context_backward_workspace_bytes")
 CASES = ("sequence_bos", "sequence_start")
@@ -226,24 +225,7 @@ def test_a_forced_kernel_route_on_host_tensors_is_an_error():
 
 
 # ------------------------------------------------------------------ the C ABI without a GPU
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_sequence_supported.restype = ci
-    lib.mmfs_sequence_supported.argtypes = [ci, i64]
-    lib.mmfs_sequence_index.restype = ci
-    lib.mmfs_sequence_index.argtypes = [vp] + [i64] * 6 + [vp] * 7
-    lib.mmfs_sequence_embed_forward.restype = ci
-    lib.mmfs_sequence_embed_forward.argtypes = [ci, ci] + [vp] * 4 + [i64, vp, vp] + [i64] * 3 + [vp]
-    lib.mmfs_sequence_embed_backward.restype = ci
-    lib.mmfs_sequence_embed_backward.argtypes = [ci, ci] + [vp] * 9 + [i64] * 5 + [vp]
-    lib.mmfs_sequence_context_forward.restype = ci
-    lib.mmfs_sequence_context_forward.argtypes = [ci] + [vp] * 9 + [i64] * 6 + [vp]
-    lib.mmfs_sequence_context_backward_workspace_bytes.restype = i64
-    lib.mmfs_sequence_context_backward_workspace_bytes.argtypes = [ci, i64, i64]
-    lib.mmfs_sequence_context_backward.restype = ci
-    lib.mmfs_sequence_context_backward.argtypes = [ci] + [vp] * 9 + [i64] * 6 + [vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -253,7 +235,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
     assert "mmfs_sequence_supported" in raw[raw.index("#define MMFS_MSDA_ABI_VERSION"):raw.index("enum mmfs_dtype")]

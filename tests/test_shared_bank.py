@@ -1,7 +1,6 @@
 """CPU-side checks of the shared value bank (one bank of Bv rows serving B = g * Bv query rows, include/mmfs_msda.h
 MMFS_BANK_*): the C ABI exports its two entries and refuses bad maps without touching a GPU, the host-side row map is the
 index order of ``torch.cat([x] * g)`` / ``x.repeat_interleave(g, 0)``, and the shim's argument checks."""
-import ctypes
 import os
 import re
 import sys
@@ -12,19 +11,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mm-interleaved_amd")]
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 E_DIMS, E_UNSUPPORTED = -2, -5
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
 
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    lib.mmfs_msda_forward_shared.restype = _int
-    lib.mmfs_msda_forward_shared.argtypes = [_int] + [_vp] * 6 + [_i64] * 2 + [_int] + [_i64] * 6 + [ctypes.c_uint, _vp]
-    lib.mmfs_sample_forward_heads_shared.restype = _int
-    lib.mmfs_sample_forward_heads_shared.argtypes = ([_int] + [_vp] * 5 + [_i64] * 2 + [_vp] * 8 + [_i64] * 2 + [_int]
-                                                     + [_i64] * 10 + [_vp])
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_library_exports_the_shared_entries_at_abi_14():
@@ -34,7 +24,6 @@ def test_library_exports_the_shared_entries_at_abi_14():
     text = open(HEADER).read()
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", text).group(1)) == 14
     assert re.search(r"#define\s+MMFS_BANK_TILE\s+0\b", text) and re.search(r"#define\s+MMFS_BANK_INTERLEAVE\s+1\b", text)
-    lib.mmfs_msda_abi_version.restype = _int
     assert lib.mmfs_msda_abi_version() == 14
 
 

@@ -21,7 +21,6 @@ tl = importlib.import_module("mmfs_amd.text_loss")      # (the package exports t
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 NAMES = ("mmfs_text_loss_supported", "mmfs_text_loss_forward", "mmfs_text_loss_backward")
 CASES = ("plain", "noimage", "offset_int", "offset_list", "offset_tensor", "given")
 BAR = 1e-12
@@ -200,16 +199,7 @@ def test_a_forced_kernel_route_on_host_tensors_is_an_error():
 
 
 # ------------------------------------------------------------------ the C ABI without a GPU
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_text_loss_supported.restype = ci
-    lib.mmfs_text_loss_supported.argtypes = [ci, i64]
-    lib.mmfs_text_loss_forward.restype = ci
-    lib.mmfs_text_loss_forward.argtypes = [ci] + [vp] * 6 + [i64] * 6 + [ci, vp]
-    lib.mmfs_text_loss_backward.restype = ci
-    lib.mmfs_text_loss_backward.argtypes = [ci] + [vp] * 6 + [i64] * 6 + [ci, vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -219,7 +209,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
     for n in NAMES:
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", raw).group(1)) == 14
     assert "mmfs_text_loss_supported" in raw[raw.index("#define MMFS_MSDA_ABI_VERSION"):raw.index("enum mmfs_dtype")]

@@ -18,7 +18,6 @@ from oracle.msda_oracle import OracleMSDAFunction
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmfs_msda.h")
-LIB = os.path.join(ROOT, "mm-interleaved_amd", "libmmfs_msda.so")
 Hidden = namedtuple("Hidden", "last_hidden_state")
 
 
@@ -211,18 +210,7 @@ def test_module_switch_is_off_by_default_and_leaves_the_state_dict_alone():
 
 
 # ------------------------------------------------------------------ C ABI, host side
-def _lib():
-    lib = ctypes.CDLL(LIB)
-    i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-    lib.mmfs_deform_plan_supported.restype = ci
-    lib.mmfs_deform_plan_supported.argtypes = [ci] + [i64] * 4
-    lib.mmfs_deform_plan_forward.restype = ci
-    lib.mmfs_deform_plan_forward.argtypes = [ci, vp, vp, i64, i64, vp, vp, vp, vp] + [i64] * 8 + [vp]
-    lib.mmfs_deform_plan_backward.restype = ci
-    lib.mmfs_deform_plan_backward.argtypes = [ci] + [vp] * 7 + [i64] * 2 + [i64] * 8 + [vp]
-    lib.mmfs_deform_sample_forward.restype = ci
-    lib.mmfs_deform_sample_forward.argtypes = [ci] + [vp] * 5 + [i64] * 2 + [vp, vp] + [i64] * 10 + [vp]
-    return lib
+from helpers import bound_library as _lib  # noqa: E402
 
 
 def test_new_symbols_are_declared_and_exported_at_abi_14():
@@ -232,7 +220,6 @@ def test_new_symbols_are_declared_and_exported_at_abi_14():
               "mmfs_deform_sample_forward"):
         assert re.search(r"\b" + n + r"\s*\(", text), n
         assert hasattr(lib, n), n
-    lib.mmfs_msda_abi_version.restype = ctypes.c_int
     assert lib.mmfs_msda_abi_version() == 14
     assert int(re.search(r"#define\s+MMFS_MSDA_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1)) == 14
 
