@@ -19,7 +19,7 @@
 // registers, transposed through LDS and stored channel-major; an image no slot shows gets zeros.
 // Deterministic (no atomics): the slots that show an image are found by ballot, walked in order.
 #include "msda_device.h"
-#include "../../include/mmfs_msda.h"
+#include "msda_host.h"
 
 namespace mmfs {
 namespace {
@@ -236,7 +236,7 @@ int mmfs_bank_gather(int dtype, int n_levels, const void *const *level_ptrs, con
     if (rc) return rc;
     if (n_slots == 0 || C == 0) return MMFS_OK;
     if (!src_index || !bank) return MMFS_E_NULLPTR;
-    const int es = dtype == MMFS_F32 ? 4 : 2;
+    const int es = mmfs::elem_size(dtype);
     if (((uintptr_t)bank % es)) return MMFS_E_ALIGN;
     const int c_tiles = (int)((C + kTile - 1) / kTile);
     if ((int64_t)L.tiles * c_tiles > 0x7fffffffLL) return MMFS_E_DIMS;

@@ -131,7 +131,7 @@ extern "C" int mmfs_bank_quantize_fp8(int dtype, const void *x, int64_t nbanks, 
                                       void *q, float *scale, void *stream)
 {
     using namespace mmfs;
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16) return MMFS_E_DTYPE;
+    if (!elem_size(dtype)) return MMFS_E_DTYPE;
     const int64_t lim = 0x7fffffffLL;
     if (nbanks < 0 || Bv < 0 || R < 0 || C < 0 || nbanks > lim || Bv > lim || R > lim || C > lim) return MMFS_E_DIMS;
     if (C % 16) return MMFS_E_UNSUPPORTED;                                   // (C = H*D, D a multiple of 16)
@@ -140,9 +140,5 @@ extern "C" int mmfs_bank_quantize_fp8(int dtype, const void *x, int64_t nbanks, 
     if (!x || !q || !scale) return MMFS_E_NULLPTR;
     if ((((uintptr_t)x | (uintptr_t)q | (uintptr_t)scale) & 15) != 0) return MMFS_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case MMFS_F32: return (int)quantize<float>(x, rows, R, C, q, scale, st);
-        case MMFS_F16: return (int)quantize<half_t>(x, rows, R, C, q, scale, st);
-        default: return (int)quantize<bf16_t>(x, rows, R, C, q, scale, st);
-    }
+    return (int)by_type(dtype, [&](auto t) { return quantize<decltype(t)>(x, rows, R, C, q, scale, st); });
 }

@@ -16,6 +16,7 @@
 #include "../../include/mmfs_msda.h"
 #include "msda_env.h"
 #include "msda_device.h"
+#include "msda_host.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -174,12 +175,13 @@ rmsnorm_bwd(const T *__restrict__ dy, const T *__restrict__ x, const T *__restri
 // vectors of a row a lane keeps: the power of two that covers C
 int norm_nv(int dtype, int64_t C)
 {
-    const int64_t per_lane = (C / (16 / (dtype == MMFS_F32 ? 4 : 2)) + 63) / 64;
+    const int64_t per_lane = (C / (16 / elem_size(dtype)) + 63) / 64;
     int nv = 1;
     while (nv < per_lane) nv *= 2;
     return nv;
 }
 
+// KERNEL<T, nv> (nv: norm_nv of the row length); inside by_type's lambda, T its storage type
 #define MMFS_NORM_DISPATCH(KERNEL, T, ...)                                                                        \
     switch (nv) {                                                                                                 \
         case 1: hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;    \
@@ -202,7 +204,7 @@ extern "C" {
 
 int mmfs_rmsnorm_supported(int dtype, int64_t C)
 {
-    const int es = dtype == MMFS_F32 ? 4 : (dtype == MMFS_F16 || dtype == MMFS_BF16) ? 2 : 0;
+    const int es = mmfs::elem_size(dtype);
     if (!es || C <= 0) return 0;
     const int64_t n = 16 / es;
     return C % n == 0 && C / n <= 64 * mmfs::kNormMaxVec;
@@ -211,7 +213,7 @@ int mmfs_rmsnorm_supported(int dtype, int64_t C)
 int mmfs_rmsnorm_forward(int dtype, const void *x, const void *weight, void *y, float *rstd,
                          int64_t rows, int64_t C, float eps, void *stream)
 {
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16) return MMFS_E_DTYPE;
+    if (!mmfs::elem_size(dtype)) return MMFS_E_DTYPE;
     if (rows < 0 || C < 0) return MMFS_E_DIMS;
     if (rows == 0 || C == 0) return MMFS_OK;
     if (!mmfs_rmsnorm_supported(dtype, C)) return MMFS_E_UNSUPPORTED;
@@ -221,18 +223,17 @@ int mmfs_rmsnorm_forward(int dtype, const void *x, const void *weight, void *y, 
     const int grid = mmfs::norm_grid(rows);
     using namespace mmfs;
     const int nv = norm_nv(dtype, C);
-    switch (dtype) {
-        case MMFS_F32: MMFS_NORM_DISPATCH(rmsnorm_fwd, float, (const float *)x, (const float *)weight, (float *)y, rstd, rows, (int)C, eps); break;
-        case MMFS_F16: MMFS_NORM_DISPATCH(rmsnorm_fwd, half_t, (const half_t *)x, (const half_t *)weight, (half_t *)y, rstd, rows, (int)C, eps); break;
-        default: MMFS_NORM_DISPATCH(rmsnorm_fwd, bf16_t, (const bf16_t *)x, (const bf16_t *)weight, (bf16_t *)y, rstd, rows, (int)C, eps); break;
-    }
-    return (int)hipGetLastError();
+    return by_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        MMFS_NORM_DISPATCH(rmsnorm_fwd, T, (const T *)x, (const T *)weight, (T *)y, rstd, rows, (int)C, eps);
+        return (int)hipGetLastError();
+    });
 }
 
 static int rmsnorm_backward_impl(int dtype, const void *grad_y, const void *x, const void *weight, const float *rstd,
                                  void *grad_x, float *gw, int64_t rows, int64_t C, int grid, int partials, void *stream)
 {
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16) return MMFS_E_DTYPE;
+    if (!mmfs::elem_size(dtype)) return MMFS_E_DTYPE;
     if (rows < 0 || C < 0) return MMFS_E_DIMS;
     if (rows == 0 || C == 0) return MMFS_OK;
     if (!mmfs_rmsnorm_supported(dtype, C)) return MMFS_E_UNSUPPORTED;
@@ -241,12 +242,11 @@ static int rmsnorm_backward_impl(int dtype, const void *grad_y, const void *x, c
     hipStream_t st = (hipStream_t)stream;
     using namespace mmfs;
     const int nv = norm_nv(dtype, C);
-    switch (dtype) {
-        case MMFS_F32: MMFS_NORM_DISPATCH(rmsnorm_bwd, float, (const float *)grad_y, (const float *)x, (const float *)weight, rstd, (float *)grad_x, gw, rows, (int)C, partials); break;
-        case MMFS_F16: MMFS_NORM_DISPATCH(rmsnorm_bwd, half_t, (const half_t *)grad_y, (const half_t *)x, (const half_t *)weight, rstd, (half_t *)grad_x, gw, rows, (int)C, partials); break;
-        default: MMFS_NORM_DISPATCH(rmsnorm_bwd, bf16_t, (const bf16_t *)grad_y, (const bf16_t *)x, (const bf16_t *)weight, rstd, (bf16_t *)grad_x, gw, rows, (int)C, partials); break;
-    }
-    return (int)hipGetLastError();
+    return by_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        MMFS_NORM_DISPATCH(rmsnorm_bwd, T, (const T *)grad_y, (const T *)x, (const T *)weight, rstd, (T *)grad_x, gw, rows, (int)C, partials);
+        return (int)hipGetLastError();
+    });
 }
 
 int mmfs_rmsnorm_backward(int dtype, const void *grad_y, const void *x, const void *weight, const float *rstd,

@@ -376,8 +376,8 @@ static hipError_t dispatch_bwd(const void *value, const int64_t *shapes, const i
 
 bool bwd_has_vector_path(int dtype, const Dims &d)
 {
-    if (dtype == 3) return false;
-    const int vec = dtype == 0 ? 4 : 8;
+    if (!elem_size(dtype)) return false;            // (fp64: the scalar kernel alone)
+    const int vec = 16 / elem_size(dtype);
     if (d.D % vec) return false;
     const int lpi = d.D / vec;
     return lpi >= 1 && lpi <= 64 && (lpi & (lpi - 1)) == 0;
@@ -400,10 +400,10 @@ hipError_t backward_taps(int dtype, const void *value, const int64_t *shapes, co
     if (routed && scatter) return hipErrorInvalidValue;
     const LevelSel &s = routed ? *sel : all;
     switch (dtype) {
-        case 0: return dispatch_bwd<float>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
-        case 1: return dispatch_bwd<half_t>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
-        case 2: return dispatch_bwd<bf16_t>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
-        case 3: if (routed) return hipErrorInvalidValue;
+        case MMFS_F32: return dispatch_bwd<float>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
+        case MMFS_F16: return dispatch_bwd<half_t>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
+        case MMFS_BF16: return dispatch_bwd<bf16_t>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, scatter, st, s);
+        case MMFS_F64: if (routed) return hipErrorInvalidValue;
                 return launch_scalar<double>(value, shapes, start, loc, attn, grad_out, gv, gl, ga, d, st);
         default: return hipErrorInvalidValue;
     }
@@ -437,10 +437,10 @@ hipError_t cast_from_f32(int dtype, const float *src, void *dst, int64_t n, hipS
     if (n <= 0) return hipSuccess;
     const int64_t blocks = std::min<int64_t>((n / 4 + kThreads) / kThreads, 256 * 16);
     switch (dtype) {
-        case 0: hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, 256 * 16)), dim3(kThreads), 0, st,
+        case MMFS_F32: hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, 256 * 16)), dim3(kThreads), 0, st,
                                    src, (float *)dst, n); break;
-        case 1: hipLaunchKernelGGL((cast_kernel<half_t>), dim3((unsigned)blocks), dim3(kThreads), 0, st, src, (half_t *)dst, n); break;
-        case 2: hipLaunchKernelGGL((cast_kernel<bf16_t>), dim3((unsigned)blocks), dim3(kThreads), 0, st, src, (bf16_t *)dst, n); break;
+        case MMFS_F16: hipLaunchKernelGGL((cast_kernel<half_t>), dim3((unsigned)blocks), dim3(kThreads), 0, st, src, (half_t *)dst, n); break;
+        case MMFS_BF16: hipLaunchKernelGGL((cast_kernel<bf16_t>), dim3((unsigned)blocks), dim3(kThreads), 0, st, src, (bf16_t *)dst, n); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

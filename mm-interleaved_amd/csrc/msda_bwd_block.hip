@@ -1077,7 +1077,7 @@ KeptCfg kept_config(int es, const Dims &d, const TileParams &tp, bool compact)
 
 bool sort_keeps_samples(int dtype, const Dims &d, const TileParams &tp)
 {
-    const int es = dtype == 0 ? 4 : 2;
+    const int es = elem_size(dtype);
     const bool compact = es == 2 && tile_reduce_supported(dtype, d);
     const KeptCfg c = kept_config(es, d, tp, compact);
     return c.nv > 0 && (int64_t)d.Nq * c.g <= kThreads * kScanUnroll && sort_window_bytes(d, tp, compact) > kMaxTileCells * 4u;
@@ -1116,7 +1116,7 @@ struct Scratch {
 
 Scratch carve(void *workspace, int dtype, const Dims &d)
 {
-    const int64_t es = dtype == 0 ? 4 : 2;
+    const int64_t es = elem_size(dtype);
     const int64_t pts = (int64_t)d.B * d.Nq * d.H * d.L * d.P;
     auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
     Scratch s;
@@ -1244,52 +1244,43 @@ hipError_t launch_sort(const int64_t *shapes, const int64_t *start, const Scratc
     const uint32_t win = sort_window_bytes(d, tp, compact);
     TileReduceArgs ta = tile_args(sc, d);
     ta.g_loc = g_loc; ta.g_attn = g_attn;
-    auto go_ts = [&](auto tag_compact, auto tag_threads, auto tag_ts) {
-        constexpr bool C = decltype(tag_compact)::value;
-        constexpr int THREADS = decltype(tag_threads)::value;
-        constexpr bool TS = decltype(tag_ts)::value && C && NV > 0;       // (only the kept scan of the compact records serves it)
-        static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_cell_sort<T, NV, C, THREADS, TS>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSortWindow);
-        (void)once;
-        hipLaunchKernelGGL((msda_bwd_cell_sort<T, NV, C, THREADS, TS>), dim3((unsigned)blocks), dim3(THREADS), win, st,
-                           (const T *)sc.loc_t, (const T *)sc.attn_t, sc.records, sc.cursor, sc.celltab, sc.hdr, d, tp,
-                           cell_stride_of(d), win, ta);
+    // one launcher: compact records / lanes / scan unroll as tags, the taps-sorted variant where the route asks for it
+    auto go = [&](auto tag_compact, auto tag_threads, auto tag_unroll) {
+        auto launch = [&](auto tag_ts) {
+            constexpr bool C = decltype(tag_compact)::value;
+            constexpr int THREADS = decltype(tag_threads)::value, UNROLL = decltype(tag_unroll)::value;
+            constexpr bool TS = decltype(tag_ts)::value && C && NV > 0;       // (only the kept scan of the compact records serves it)
+            static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_cell_sort<T, NV, C, THREADS, TS, UNROLL>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSortWindow);
+            (void)once;
+            hipLaunchKernelGGL((msda_bwd_cell_sort<T, NV, C, THREADS, TS, UNROLL>), dim3((unsigned)blocks), dim3(THREADS), win, st,
+                               (const T *)sc.loc_t, (const T *)sc.attn_t, sc.records, sc.cursor, sc.celltab, sc.hdr, d, tp,
+                               cell_stride_of(d), win, ta);
+        };
+        if (d.taps_sorted) launch(std::true_type()); else launch(std::false_type());
     };
-    // Two vectors of locations per query (P = 8 of 16-bit storage: the decoders' geometry) in a 1024-lane workgroup: the
-    // samples' words do not fit next to their keys, so every placing pass reads loc / attn AGAIN -- and a tile of more
-    // records than the window holds (the SD block: 32 768 samples per level) places in two passes: three reads of the
-    // level's words in all (641 MB of traffic for 101 MB of input, VERDICT r5).  512 lanes with eight samples each keep the
-    // words in registers (256 a lane): one read.  MMFS_SORT_WIDE=0: the 1024-lane kernel
-    auto go_wide = [&](auto tag_ts) {
-        constexpr bool TS = decltype(tag_ts)::value && NV > 0;
-        constexpr int THREADS = kMidThreads, UNROLL = 2 * kScanUnroll;
-        static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_bwd_cell_sort<T, NV, true, THREADS, TS, UNROLL>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSortWindow);
-        (void)once;
-        hipLaunchKernelGGL((msda_bwd_cell_sort<T, NV, true, THREADS, TS, UNROLL>), dim3((unsigned)blocks), dim3(THREADS), win, st,
-                           (const T *)sc.loc_t, (const T *)sc.attn_t, sc.records, sc.cursor, sc.celltab, sc.hdr, d, tp,
-                           cell_stride_of(d), win, ta);
-    };
-    auto go = [&](auto tag_compact, auto tag_threads) {
-        if (d.taps_sorted) go_ts(tag_compact, tag_threads, std::true_type());
-        else go_ts(tag_compact, tag_threads, std::false_type());
-    };
-    const int lanes = sort_lanes(d, vgroups, NV);
-    if constexpr ((NV == 2 || NV == 1) && sizeof(T) == 2) {
-        const char *e = knob_str(K_SORT_WIDE);
-        // (one-vector queries -- P = 4: the north star -- only when asked, "2": measured in r06x)
-        if (compact && lanes == kThreads && !(e && e[0] == '0') && (NV == 2 || (e && e[0] == '2'))) {
-            if (d.taps_sorted) go_wide(std::true_type()); else go_wide(std::false_type());
-            return hipGetLastError();
-        }
-    }
     typedef std::integral_constant<bool, sizeof(T) == 2> Compact;
     typedef std::integral_constant<bool, false> Wide;
     typedef std::integral_constant<int, kThreads> Big;
     typedef std::integral_constant<int, kMidThreads> Mid;
     typedef std::integral_constant<int, kSmallThreads> Small;
-    if (compact) { if (lanes == kSmallThreads) go(Compact(), Small()); else if (lanes == kMidThreads) go(Compact(), Mid()); else go(Compact(), Big()); }
-    else { if (lanes == kSmallThreads) go(Wide(), Small()); else if (lanes == kMidThreads) go(Wide(), Mid()); else go(Wide(), Big()); }
+    typedef std::integral_constant<int, kScanUnroll> Unroll;
+    // Two vectors of locations per query (P = 8 of 16-bit storage: the decoders' geometry) in a 1024-lane workgroup: the
+    // samples' words do not fit next to their keys, so every placing pass reads loc / attn AGAIN -- and a tile of more
+    // records than the window holds (the SD block: 32 768 samples per level) places in two passes: three reads of the
+    // level's words in all (641 MB of traffic for 101 MB of input, VERDICT r5).  512 lanes with eight samples each keep the
+    // words in registers (256 a lane): one read.  MMFS_SORT_WIDE=0: the 1024-lane kernel
+    const int lanes = sort_lanes(d, vgroups, NV);
+    if constexpr ((NV == 2 || NV == 1) && sizeof(T) == 2) {
+        const char *e = knob_str(K_SORT_WIDE);
+        // (one-vector queries -- P = 4: the north star -- only when asked, "2": measured in r06x)
+        if (compact && lanes == kThreads && !(e && e[0] == '0') && (NV == 2 || (e && e[0] == '2'))) {
+            go(std::true_type(), Mid(), std::integral_constant<int, 2 * kScanUnroll>());
+            return hipGetLastError();
+        }
+    }
+    if (compact) { if (lanes == kSmallThreads) go(Compact(), Small(), Unroll()); else if (lanes == kMidThreads) go(Compact(), Mid(), Unroll()); else go(Compact(), Big(), Unroll()); }
+    else { if (lanes == kSmallThreads) go(Wide(), Small(), Unroll()); else if (lanes == kMidThreads) go(Wide(), Mid(), Unroll()); else go(Wide(), Big(), Unroll()); }
     return hipGetLastError();
 }
 
@@ -1314,22 +1305,18 @@ hipError_t launch_reduce(const Scratch &sc, const void *go, void *gv, const Dims
     const int chunks = (int)chunks64;
     const int64_t blocks = (int64_t)d.B * d.H * chunks;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((int64_t)d.Nq * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes)
-        hipLaunchKernelGGL((msda_bwd_block_reduce<T, LPS, true>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
-                           (const T *)go, (T *)gv, sc.records, sc.celltab, sc.hdr, d, chunks, cell_stride_of(d),
-                           sc.ovf, sc.oslots, sc.oentries, sc.oacc);
-    else
-        hipLaunchKernelGGL((msda_bwd_block_reduce<T, LPS, false>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
-                           (const T *)go, (T *)gv, sc.records, sc.celltab, sc.hdr, d, chunks, cell_stride_of(d),
-                           sc.ovf, sc.oslots, sc.oentries, sc.oacc);
-    // long lists (normally none: both kernels read the queue length on the device and return)
     const unsigned oblocks = std::min<unsigned>(sc.cap_entries, 512u) * kOvfLanes;
-    if ((int64_t)d.Nq * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes)
-        hipLaunchKernelGGL((msda_bwd_block_overflow<T, LPS, true>), dim3(oblocks), dim3(kRThreads), 0, st,
+    // BUF: a (b) slab of grad_out within a buffer descriptor's reach -- one decision for both kernels
+    auto go_buf = [&](auto buf) {
+        constexpr bool BUF = decltype(buf)::value;
+        hipLaunchKernelGGL((msda_bwd_block_reduce<T, LPS, BUF>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
+                           (const T *)go, (T *)gv, sc.records, sc.celltab, sc.hdr, d, chunks, cell_stride_of(d),
+                           sc.ovf, sc.oslots, sc.oentries, sc.oacc);
+        // long lists (normally none: both kernels read the queue length on the device and return)
+        hipLaunchKernelGGL((msda_bwd_block_overflow<T, LPS, BUF>), dim3(oblocks), dim3(kRThreads), 0, st,
                            (const T *)go, (T *)gv, sc.records, sc.ovf, sc.oslots, sc.oentries, sc.oacc, d);
-    else
-        hipLaunchKernelGGL((msda_bwd_block_overflow<T, LPS, false>), dim3(oblocks), dim3(kRThreads), 0, st,
-                           (const T *)go, (T *)gv, sc.records, sc.ovf, sc.oslots, sc.oentries, sc.oacc, d);
+    };
+    if ((int64_t)d.Nq * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes) go_buf(std::true_type()); else go_buf(std::false_type());
     hipLaunchKernelGGL((msda_bwd_block_ovf_store<T>), dim3(std::min<unsigned>(sc.cap_slots, 1024u)), dim3(256), 0, st,
                        (T *)gv, sc.ovf, sc.oslots, sc.oacc, d);
     return hipGetLastError();
@@ -1355,7 +1342,7 @@ bool bwd_value_block_supported(int dtype, const Dims &d)
 {
     if (!bwd_value_tiled_supported(dtype, d)) return false;
     if (d.L > kMaxLevels) return false;
-    const int vec = dtype == 0 ? 4 : 8;
+    const int vec = 16 / elem_size(dtype);
     const int lps = d.D / vec;
     if (lps < 4 || lps > 32) return false;
     if (2LL * d.S + 2LL * d.L > 0x3fffffffLL) return false;
@@ -1379,23 +1366,25 @@ const int *value_table_refused_flag(void *workspace, int dtype, const Dims &d)
 // (the workspace starts with the same three pieces as the pixel-stationary layout -- re-packed
 // loc, re-packed attn, level cursors -- so backward_value_prepare serves both)
 
+// The sort reads loc / attn where they are, so nothing is re-packed: the stand-alone prepare and the prepare folded into
+// a taps kernel (value_prepare_job) must plan the same sort for the same call.  MMFS_SORT_REPACK=1: always re-pack
+static bool sort_reads_in_place(int dtype, const void *loc, const void *attn, const Dims &d, const TileParams &tp)
+{
+    const bool aligned = (uintptr_t)loc % 16 == 0 && (uintptr_t)attn % 8 == 0;
+    const char *e = knob_str(K_SORT_REPACK);
+    return aligned && sort_keeps_samples(dtype, d, tp) && !(e && e[0] == '1');
+}
+
 // Stage 2a for this generation: re-pack + cursors (+ the plan when the level table is at hand), one launch.
 hipError_t backward_value_block_prepare(int dtype, const void *loc, const void *attn, const int64_t *shapes,
                                         const int64_t *start, void *workspace, const Dims &d, hipStream_t st)
 {
     if (!bwd_value_block_supported(dtype, d)) return hipErrorInvalidValue;
-    const int es = dtype == 0 ? 4 : 2;
+    const int es = elem_size(dtype);
     const Scratch sc = carve(workspace, dtype, d);
-    auto gran = [](const void *a, const void *b, int chunk_bytes) {
-        const bool al = (((uintptr_t)a | (uintptr_t)b) % 16) == 0;
-        if (al && chunk_bytes % 16 == 0) return 16;
-        if (al && chunk_bytes % 8 == 0) return 8;
-        if (al && chunk_bytes % 4 == 0) return 4;
-        return 2;
-    };
     const int cl = d.P * 2 * es, ca = d.P * es;
     if (ca % 2) return hipErrorInvalidValue;
-    const int vb_l = gran(loc, sc.loc_t, cl), vb_a = gran(attn, sc.attn_t, ca);
+    const int vb_l = repack_copy_bytes(loc, sc.loc_t, cl), vb_a = repack_copy_bytes(attn, sc.attn_t, ca);
     const int vpc_l = cl / vb_l, vpc_a = ca / vb_a;
     const int64_t groups = (int64_t)d.B * d.Nq * d.H * d.L;
     int64_t total_l = groups * vpc_l, total_a = groups * vpc_a;
@@ -1404,10 +1393,7 @@ hipError_t backward_value_block_prepare(int dtype, const void *loc, const void *
     if (shapes != nullptr && start != nullptr) {
         const TileParams tp = make_params(d);
         pa = plan_args(shapes, start, sc, d, tp);
-        // the sort can read loc / attn where they are (the header tells it): no re-pack
-        const bool aligned = (uintptr_t)loc % 16 == 0 && (uintptr_t)attn % 8 == 0;
-        const char *e = knob_str(K_SORT_REPACK);
-        if (aligned && sort_keeps_samples(dtype, d, tp) && !(e && e[0] == '1')) {
+        if (sort_reads_in_place(dtype, loc, attn, d, tp)) {         // (the header tells the sort): no re-pack
             pa.loc_src = loc; pa.attn_src = attn;
             total_l = total_a = 0;
         }
@@ -1430,9 +1416,7 @@ bool value_prepare_job(int dtype, const void *loc, const void *attn, const int64
     const Scratch sc = carve(workspace, dtype, d);
     job->pa = plan_args(shapes, start, sc, d, tp);
     job->cursor = sc.cursor; job->cursor_words = sc.cursor_bytes / 4;
-    const bool aligned = (uintptr_t)loc % 16 == 0 && (uintptr_t)attn % 8 == 0;
-    const char *e = knob_str(K_SORT_REPACK);
-    if (!aligned || !sort_keeps_samples(dtype, d, tp) || (e && e[0] == '1')) return false;
+    if (!sort_reads_in_place(dtype, loc, attn, d, tp)) return false;
     job->pa.loc_src = loc; job->pa.attn_src = attn;
     return true;
 }
@@ -1443,12 +1427,7 @@ hipError_t backward_value_block_sort(int dtype, const int64_t *shapes, const int
     if (!bwd_value_block_supported(dtype, d)) return hipErrorInvalidValue;
     if (d.taps_sorted && !(taps_sorted_supported(dtype, d) && g_loc && g_attn)) return hipErrorInvalidValue;
     const Scratch sc = carve(workspace, dtype, d);
-    switch (dtype) {
-        case 0: return dispatch_sort<float>(shapes, start, sc, d, planned, st, g_loc, g_attn);
-        case 1: return dispatch_sort<half_t>(shapes, start, sc, d, planned, st, g_loc, g_attn);
-        case 2: return dispatch_sort<bf16_t>(shapes, start, sc, d, planned, st, g_loc, g_attn);
-        default: return hipErrorInvalidValue;
-    }
+    return by_type(dtype, [&](auto t) { return dispatch_sort<decltype(t)>(shapes, start, sc, d, planned, st, g_loc, g_attn); });
 }
 
 // grad_loc / grad_attn from the cell-sorted records (msda_bwd_taps_sorted.hip) need: the matrix-core reduce's 8-byte records
@@ -1490,22 +1469,12 @@ hipError_t backward_value_block_reduce(int dtype, const void *grad_out, void *gr
     if (!bwd_value_block_supported(dtype, d)) return hipErrorInvalidValue;
     const Scratch sc = carve(workspace, dtype, d);
     // rows no level owns (only a table the HOST has not vouched for can have them)
-    if (!all_rows_owned) switch (dtype) {
-        case 0: launch_zero_uncovered<float>(grad_value, sc, d, st); break;
-        case 1: launch_zero_uncovered<half_t>(grad_value, sc, d, st); break;
-        case 2: launch_zero_uncovered<bf16_t>(grad_value, sc, d, st); break;
-        default: break;
-    }
+    if (!all_rows_owned) by_type(dtype, [&](auto t) { launch_zero_uncovered<decltype(t)>(grad_value, sc, d, st); });
     if (sc.th != nullptr) {
         const TileReduceArgs a = tile_args(sc, d);
         return tile_reduce(dtype, grad_out, grad_value, a, d, sc.tile_cap_extra, st);
     }
-    switch (dtype) {
-        case 0: return dispatch_reduce<float>(sc, grad_out, grad_value, d, st);
-        case 1: return dispatch_reduce<half_t>(sc, grad_out, grad_value, d, st);
-        case 2: return dispatch_reduce<bf16_t>(sc, grad_out, grad_value, d, st);
-        default: return hipErrorInvalidValue;
-    }
+    return by_type(dtype, [&](auto t) { return dispatch_reduce<decltype(t)>(sc, grad_out, grad_value, d, st); });
 }
 
 }  // namespace mmfs

@@ -103,7 +103,7 @@ hipError_t run(const int *flag, const int64_t *shapes, const int64_t *start, con
 
 int64_t refused_table_scratch_bytes(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return 0;
+    if (dtype != MMFS_F16 && dtype != MMFS_BF16) return 0;
     const int64_t n_value = (int64_t)d.B * d.S * d.H * d.D;
     return ((n_value + 3) / 4 * 16 + 255) / 256 * 256;
 }
@@ -114,9 +114,9 @@ hipError_t backward_value_refused_table(int dtype, const int64_t *shapes, const 
 {
     const int *flag = value_table_refused_flag(workspace, dtype, d);
     switch (dtype) {
-        case 0: return run<float>(flag, shapes, start, loc, attn, grad_out, grad_value, nullptr, d, st);
-        case 1: return run<half_t>(flag, shapes, start, loc, attn, grad_out, grad_value, acc, d, st);
-        case 2: return run<bf16_t>(flag, shapes, start, loc, attn, grad_out, grad_value, acc, d, st);
+        case MMFS_F32: return run<float>(flag, shapes, start, loc, attn, grad_out, grad_value, nullptr, d, st);
+        case MMFS_F16: return run<half_t>(flag, shapes, start, loc, attn, grad_out, grad_value, acc, d, st);
+        case MMFS_BF16: return run<bf16_t>(flag, shapes, start, loc, attn, grad_out, grad_value, acc, d, st);
         default: return hipErrorInvalidValue;
     }
 }

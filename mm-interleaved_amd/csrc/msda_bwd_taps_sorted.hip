@@ -455,11 +455,10 @@ hipError_t backward_taps_sorted(int dtype, const void *value, const void *grad_o
     uint32_t cap_extra = 0;
     const blk::TileReduceArgs a = blk::taps_sorted_args(workspace, dtype, d, &cap_extra);
     if (!a.xdesc) return hipErrorInvalidValue;
-    switch (dtype) {
-        case 1: return blk::dispatch_taps<half_t>(value, grad_out, grad_loc, grad_attn, a, d, cap_extra, st);
-        case 2: return blk::dispatch_taps<bf16_t>(value, grad_out, grad_loc, grad_attn, a, d, cap_extra, st);
-        default: return hipErrorInvalidValue;
-    }
+    // (16-bit storage alone: taps_sorted_supported has refused the others)
+    return by_half_type(dtype, [&](auto t) {
+        return blk::dispatch_taps<decltype(t)>(value, grad_out, grad_loc, grad_attn, a, d, cap_extra, st);
+    });
 }
 
 }  // namespace mmfs

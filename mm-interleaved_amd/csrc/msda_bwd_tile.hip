@@ -504,7 +504,7 @@ extern "C" int mmfs_debug_tile_profile(unsigned long long *out, int reset)
 
 bool tile_reduce_supported(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return false;
+    if (dtype != MMFS_F16 && dtype != MMFS_BF16) return false;
     if (d.D != 32 && d.D != 64 && d.D != 128) return false;
     if (d.L > kMaxLevels) return false;
     if (const char *e = knob_str(K_VALUE_ALGO)) if (e[0] == 'b' || e[0] == 'p') return false;       // "block", "pixel"
@@ -520,11 +520,8 @@ bool tile_reduce_supported(int dtype, const Dims &d)
 hipError_t tile_reduce(int dtype, const void *grad_out, void *grad_value, const TileReduceArgs &a, const Dims &d,
                        uint32_t cap_extra, hipStream_t st)
 {
-    switch (dtype) {
-        case 1: return dispatch_tile<half_t>(grad_out, grad_value, a, d, cap_extra, st);
-        case 2: return dispatch_tile<bf16_t>(grad_out, grad_value, a, d, cap_extra, st);
-        default: return hipErrorInvalidValue;
-    }
+    if (dtype != MMFS_F16 && dtype != MMFS_BF16) return hipErrorInvalidValue;
+    return by_half_type(dtype, [&](auto t) { return dispatch_tile<decltype(t)>(grad_out, grad_value, a, d, cap_extra, st); });
 }
 
 }  // namespace blk

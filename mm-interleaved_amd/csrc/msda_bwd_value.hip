@@ -458,12 +458,8 @@ repack_kernel(const char *__restrict__ src, char *__restrict__ dst, int B, int N
 
 static hipError_t repack(const void *src, void *dst, const Dims &d, int chunk_bytes, hipStream_t st)
 {
-    const bool al = (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
-    int vb = 2;
-    if (al && chunk_bytes % 16 == 0) vb = 16;
-    else if (al && chunk_bytes % 8 == 0) vb = 8;
-    else if (al && chunk_bytes % 4 == 0) vb = 4;
-    else if (chunk_bytes % 2) return hipErrorInvalidValue;
+    const int vb = repack_copy_bytes(src, dst, chunk_bytes);
+    if (chunk_bytes % vb) return hipErrorInvalidValue;           // (an odd chunk)
     const int vpc = chunk_bytes / vb;
     const int64_t total = (int64_t)d.B * d.Nq * d.H * d.L * vpc;
     const int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 64);
@@ -503,7 +499,7 @@ struct Scratch {           // carved from the caller's workspace, 16-byte aligne
 
 Scratch carve(void *workspace, int dtype, const Dims &d)
 {
-    const int64_t es = dtype == 0 ? 4 : 2;
+    const int64_t es = elem_size(dtype);
     const int64_t pts = (int64_t)d.B * d.Nq * d.H * d.L * d.P;
     auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
     Scratch s;
@@ -541,12 +537,12 @@ hipError_t launch_reduce(const Scratch &sc, const void *go, void *gv, const Dims
     const int chunks = (d.S + GROUPS - 1) / GROUPS;
     const int64_t blocks = (int64_t)d.B * d.H * chunks;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((int64_t)d.Nq * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes)
-        hipLaunchKernelGGL((msda_bwd_value_reduce<T, LPS, true>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
+    // BUF: a (b) slab of grad_out within a buffer descriptor's reach
+    auto go_buf = [&](auto buf) {
+        hipLaunchKernelGGL((msda_bwd_value_reduce<T, LPS, decltype(buf)::value>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
                            (const T *)go, (T *)gv, sc.records, sc.pixtab, d, chunks);
-    else
-        hipLaunchKernelGGL((msda_bwd_value_reduce<T, LPS, false>), dim3((unsigned)blocks), dim3(kRThreads), 0, st,
-                           (const T *)go, (T *)gv, sc.records, sc.pixtab, d, chunks);
+    };
+    if ((int64_t)d.Nq * d.H * d.D * (int64_t)sizeof(T) <= kMaxSlabBytes) go_buf(std::true_type()); else go_buf(std::false_type());
     return hipGetLastError();
 }
 
@@ -605,7 +601,7 @@ hipError_t backward_value_prepare(int dtype, const void *loc, const void *attn, 
         return backward_value_block_prepare(dtype, loc, attn, planned ? shapes : nullptr, planned ? start : nullptr,
                                             workspace, d, st);
     }
-    const int es = dtype == 0 ? 4 : 2;
+    const int es = elem_size(dtype);
     const Scratch sc = carve(workspace, dtype, d);
     hipError_t e = mmfs::zero_fill(sc.cursor, (size_t)sc.cursor_bytes, st);
     if (e != hipSuccess) return e;
@@ -622,12 +618,7 @@ hipError_t backward_value_sort(int dtype, const int64_t *shapes, const int64_t *
     if (bwd_value_block_supported(dtype, d))
         return backward_value_block_sort(dtype, shapes, start, workspace, d, planned, st);
     const Scratch sc = carve(workspace, dtype, d);
-    switch (dtype) {
-        case 0: return dispatch_sort<float>(shapes, start, sc, d, st);
-        case 1: return dispatch_sort<half_t>(shapes, start, sc, d, st);
-        case 2: return dispatch_sort<bf16_t>(shapes, start, sc, d, st);
-        default: return hipErrorInvalidValue;
-    }
+    return by_type(dtype, [&](auto t) { return dispatch_sort<decltype(t)>(shapes, start, sc, d, st); });
 }
 
 // Stage 2c: reduce every pixel's run into its grad_value row.
@@ -638,12 +629,7 @@ hipError_t backward_value_reduce(int dtype, const void *grad_out, void *grad_val
     if (bwd_value_block_supported(dtype, d))      // must mirror backward_value_sort
         return backward_value_block_reduce(dtype, grad_out, grad_value, workspace, d, all_rows_owned, st);
     const Scratch sc = carve(workspace, dtype, d);
-    switch (dtype) {
-        case 0: return dispatch_reduce<float>(sc, grad_out, grad_value, d, st);
-        case 1: return dispatch_reduce<half_t>(sc, grad_out, grad_value, d, st);
-        case 2: return dispatch_reduce<bf16_t>(sc, grad_out, grad_value, d, st);
-        default: return hipErrorInvalidValue;
-    }
+    return by_type(dtype, [&](auto t) { return dispatch_reduce<decltype(t)>(sc, grad_out, grad_value, d, st); });
 }
 
 hipError_t backward_value_run(int dtype, const int64_t *shapes, const int64_t *start,

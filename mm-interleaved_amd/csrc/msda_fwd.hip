@@ -269,10 +269,10 @@ hipError_t forward(int dtype, const void *value, const int64_t *shapes, const in
     if (algo == 2 || (algo == 0 && fwd_mma_applies(dtype, d)))
         return forward_mma(dtype, value, shapes, start, loc, attn, out, d, st);
     switch (dtype) {
-        case 0: return dispatch_fwd<float>(value, shapes, start, loc, attn, out, d, st);
-        case 1: return dispatch_fwd<half_t>(value, shapes, start, loc, attn, out, d, st);
-        case 2: return dispatch_fwd<bf16_t>(value, shapes, start, loc, attn, out, d, st);
-        case 3: return launch_scalar<double>(value, shapes, start, loc, attn, out, d, st);
+        case MMFS_F32: return dispatch_fwd<float>(value, shapes, start, loc, attn, out, d, st);
+        case MMFS_F16: return dispatch_fwd<half_t>(value, shapes, start, loc, attn, out, d, st);
+        case MMFS_BF16: return dispatch_fwd<bf16_t>(value, shapes, start, loc, attn, out, d, st);
+        case MMFS_F64: return launch_scalar<double>(value, shapes, start, loc, attn, out, d, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -299,13 +299,8 @@ static hipError_t dispatch_fwd_fp8(const void *q, const float *scale, const int6
 hipError_t forward_fp8(int dtype, const void *q, const float *scale, const int64_t *shapes, const int64_t *start,
                        const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
 {
-    if (!fwd_fp8_supported(d)) return hipErrorInvalidValue;
-    switch (dtype) {
-        case 0: return dispatch_fwd_fp8<float>(q, scale, shapes, start, loc, attn, out, d, st);
-        case 1: return dispatch_fwd_fp8<half_t>(q, scale, shapes, start, loc, attn, out, d, st);
-        case 2: return dispatch_fwd_fp8<bf16_t>(q, scale, shapes, start, loc, attn, out, d, st);
-        default: return hipErrorInvalidValue;
-    }
+    if (!fwd_fp8_supported(d) || !elem_size(dtype)) return hipErrorInvalidValue;
+    return by_type(dtype, [&](auto t) { return dispatch_fwd_fp8<decltype(t)>(q, scale, shapes, start, loc, attn, out, d, st); });
 }
 
 }  // namespace mmfs

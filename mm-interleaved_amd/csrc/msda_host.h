@@ -1,4 +1,4 @@
-// msda_host.h -- the small host-side checks and dispatchers that every extern "C" entry shares.
+// msda_host.h -- the small host-side checks and dispatchers that every extern "C" entry and every launcher shares.
 #pragma once
 #include "../../include/mmfs_msda.h"
 #include "msda_device.h"
@@ -28,8 +28,8 @@ inline int heads_rows(int64_t &ld, int64_t cols, const void *p, int64_t vec, int
     return MMFS_OK;
 }
 
-// f(T()) for the storage type of a dtype that elem_size serves without fp64
-template <typename F> int by_type(int dtype, F &&f)
+// f(T()) for the storage type of a dtype that elem_size serves without fp64; whatever f returns (a status, a hipError_t)
+template <typename F> auto by_type(int dtype, F &&f) -> decltype(f(float()))
 {
     if (dtype == MMFS_F32) return f(float());
     if (dtype == MMFS_F16) return f(half_t());
@@ -37,6 +37,20 @@ template <typename F> int by_type(int dtype, F &&f)
 }
 
 // the same for an entry that serves the two 16-bit types alone (it has refused the others)
-template <typename F> int by_half_type(int dtype, F &&f) { return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t()); }
+template <typename F> auto by_half_type(int dtype, F &&f) -> decltype(f(half_t()))
+{
+    return dtype == MMFS_F16 ? f(half_t()) : f(bf16_t());
+}
+
+// Bytes per copy (16 / 8 / 4, else 2) of a re-pack that moves chunks of ``chunk_bytes`` between these two pointers: the
+// widest access both ends are aligned for that divides the chunk.  An odd chunk has none: the caller refuses it.
+inline int repack_copy_bytes(const void *a, const void *b, int chunk_bytes)
+{
+    const bool al = (((uintptr_t)a | (uintptr_t)b) % 16) == 0;
+    if (al && chunk_bytes % 16 == 0) return 16;
+    if (al && chunk_bytes % 8 == 0) return 8;
+    if (al && chunk_bytes % 4 == 0) return 4;
+    return 2;
+}
 
 }  // namespace mmfs

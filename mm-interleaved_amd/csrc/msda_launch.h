@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "msda_device.h"
+#include "msda_host.h"      // elem_size, by_type: what the launchers dispatch a dtype code with
 
 namespace mmfs {
 
