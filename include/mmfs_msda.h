@@ -36,7 +36,10 @@
 extern "C" {
 #endif
 
-#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_llama_attn_prefill / _prefill_tiles, MMFS_LLAMA_PREFILL_*: the same attention over a prompt, see
+#define MMFS_MSDA_ABI_VERSION 14  /* 14 (additive): + mmfs_llama_attn_train_supported / _train_tiles / _train_workspace_bytes / _train_rope / _train_forward /
+                                   *     _train_backward: the same attention in training, causal, forward and backward, see "LLaMA
+                                   *     self-attention in training" below
+                                   * 14 (additive): + mmfs_llama_attn_prefill / _prefill_tiles, MMFS_LLAMA_PREFILL_*: the same attention over a prompt, see
                                    *     "LLaMA self-attention over a prompt" below
                                    * 14 (additive): + mmfs_llama_attn_supported / _rope_append / _decode_keys / _decode_workspace_bytes / _decode: the LLM's self-attention
                                    *     at decode (rotary embedding, in-place key / value cache, split-key attention), see "LLaMA self-attention at
@@ -904,6 +907,42 @@ int mmfs_llama_attn_prefill(int dtype, const void *q_rot, const void *k_cache, c
                             int64_t bias_query_stride, int64_t bias_len, unsigned flags, void *context, int64_t B, int64_t Lq,
                             int64_t H, int64_t D, int64_t cap, void *stream);
 int64_t mmfs_llama_attn_prefill_tiles(int level);
+
+/* LLaMA self-attention in training (csrc/mmfs_llama_train.hip; additive at ABI 14): what the reference's _forward_train
+ * (models/utils/monkey_patch/llama_flash_attn_train_monkey_patch.py:35-82) asks of flash_attn_func(q, k, v, 0.0, None, causal=True),
+ * forward and backward, with no tensor of size L x L.  No cache, no bias; the mask is causal, always: key t is live for query j
+ * iff t <= j.  q, k, v, q_rot, k_rot, context, grad_context, grad_q, grad_k, grad_v [B, L, H * 128] of T (MMFS_F16 / MMFS_BF16),
+ * packed, token-major; lse [B, H, L] fp32; position_ids [B, L] int64; cos_table, sin_table [max_pos, 64] fp32 as for
+ * mmfs_llama_attn_rope_append.  No entry reads anything back, allocates, clears or synchronises; no atomics: bit-reproducible,
+ * eager or replayed.  A masked score is selected, never added to: a NaN in token t's k or v reaches no query j < t.
+ * mmfs_llama_attn_train_supported: D == 128, a 16-bit type, 1 <= L <= 2^22; otherwise 0 and the calls return MMFS_E_UNSUPPORTED.
+ * mmfs_llama_attn_train_tiles: level 0 the query rows of a workgroup (forward, dq), 1 the keys of a forward tile, 2 the keys of
+ *   a dkdv workgroup, 3 the queries of a dkdv tile, 4 the query rows of a wave; any other level MMFS_E_DIMS.  Host-only.
+ * mmfs_llama_attn_train_workspace_bytes: what the backward's ``workspace`` (16-byte aligned, nothing to clear) holds: delta
+ *   [B, H, L] fp32; < 0: MMFS_E_DIMS.  Host-only.
+ * mmfs_llama_attn_train_rope: one launch.  q_rot = q cos + rotate_half(q) sin, k_rot alike (fp32, one rounding); a position outside
+ *   [0, max_pos) makes that token's q_rot and k_rot NaN.
+ * mmfs_llama_attn_train_forward: one launch.  context = softmax_t(q_rot[b, j] . k_rot[b, t] / sqrt(128)) v over t <= j, P rounded
+ *   to T before the second product; lse = ln sum_t exp(score).
+ * mmfs_llama_attn_train_backward: two launches (dq, which also writes delta = rowsum(grad_context * context) to the workspace;
+ *   then dk and dv).  Both recompute P = exp(score - lse).  grad_q and grad_k are the gradients of the UNROTATED q and k: the
+ *   inverse rotation runs on the fp32 sums, one rounding.
+ * Errors come back before any launch: MMFS_E_DTYPE (an unknown code); MMFS_E_DIMS for a negative size, B * H > 2^24, a max_pos
+ * outside [0, 2^40]; MMFS_E_UNSUPPORTED for what the query refuses (an empty L is not refused); then 0 for an empty problem (B, H
+ * or L of 0); MMFS_E_NULLPTR for a NULL required pointer; MMFS_E_ALIGN for tensors, tables and the workspace that are not 16-byte
+ * aligned (position_ids: 8, lse: 4). */
+int mmfs_llama_attn_train_supported(int dtype, int64_t D, int64_t L);
+int64_t mmfs_llama_attn_train_tiles(int level);
+int64_t mmfs_llama_attn_train_workspace_bytes(int64_t B, int64_t H, int64_t L);
+int mmfs_llama_attn_train_rope(int dtype, const void *q, const void *k, const int64_t *position_ids, const float *cos_table,
+                               const float *sin_table, int64_t max_pos, void *q_rot, void *k_rot, int64_t B, int64_t L,
+                               int64_t H, int64_t D, void *stream);
+int mmfs_llama_attn_train_forward(int dtype, const void *q_rot, const void *k_rot, const void *v, void *context, float *lse,
+                                  int64_t B, int64_t L, int64_t H, int64_t D, void *stream);
+int mmfs_llama_attn_train_backward(int dtype, const void *q_rot, const void *k_rot, const void *v, const void *context,
+                                   const void *grad_context, const float *lse, const int64_t *position_ids,
+                                   const float *cos_table, const float *sin_table, int64_t max_pos, void *grad_q, void *grad_k,
+                                   void *grad_v, float *workspace, int64_t B, int64_t L, int64_t H, int64_t D, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-image feature bank: MMFS's ``input_flatten`` built in one pass.

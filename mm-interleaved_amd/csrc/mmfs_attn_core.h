@@ -1,5 +1,5 @@
 // mmfs_attn_core.h -- what the attention kernels share (mmfs_attn.hip: the Q-Former, D = 64; mmfs_llama_attn.hip: decode,
-// mmfs_llama_prefill.hip: prefill, D = 128; mmfs_text_loss.hip takes exp_hw alone): exp by the hardware's exp2, finfo(T).min
+// mmfs_llama_prefill.hip: prefill, mmfs_llama_train.hip: training, D = 128; mmfs_text_loss.hip takes exp_hw alone): exp by the hardware's exp2, finfo(T).min
 // and the masked-key rule, the fragment helpers of the 16x16x32 matrix products, and on the host side the checks that the
 // LLaMA entries make alike.  The online-softmax tile step of qk_attn_fwd and llama_attn_prefill is NOT here: each kernel
 // keeps its loop (profiles/attn_core.md says what a shared routine measured).
@@ -89,6 +89,23 @@ inline int llama_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lq, i
     if (B < 0 || H < 0 || D < 0 || Lq < 0 || cap < 0) return MMFS_E_DIMS;
     if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
     if (!llama_supported(dtype, D, Lq, cap)) return MMFS_E_UNSUPPORTED;
+    return MMFS_OK;
+}
+
+// the training entries (mmfs_llama_train.hip): no cache, L tokens a row; an empty problem (B, H or L of 0) is no error
+constexpr int64_t kLlamaTrainMaxL = 1 << 22;
+
+inline bool llama_train_supported(int dtype, int64_t D, int64_t L)
+{
+    return (dtype == MMFS_F16 || dtype == MMFS_BF16) && D == kLlamaD && L >= 1 && L <= kLlamaTrainMaxL;
+}
+
+inline int llama_train_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t L)
+{
+    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
+    if (B < 0 || H < 0 || D < 0 || L < 0) return MMFS_E_DIMS;
+    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
+    if (!llama_train_supported(dtype, D, L ? L : 1)) return MMFS_E_UNSUPPORTED;
     return MMFS_OK;
 }
 

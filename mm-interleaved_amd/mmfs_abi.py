@@ -76,6 +76,12 @@ mmfs_llama_attn_decode_workspace_bytes          l  l3
 mmfs_llama_attn_decode                          i  i p6 i ll pp l5 p
 mmfs_llama_attn_prefill                         i  i p6 i l3 u p l5 p
 mmfs_llama_attn_prefill_tiles                   l  i
+mmfs_llama_attn_train_supported                 i  i ll
+mmfs_llama_attn_train_tiles                     l  i
+mmfs_llama_attn_train_workspace_bytes           l  l3
+mmfs_llama_attn_train_rope                      i  i p5 l pp l4 p
+mmfs_llama_attn_train_forward                   i  i p5 l4 p
+mmfs_llama_attn_train_backward                  i  i p9 l p4 l4 p
 mmfs_bank_gather                                i  ii p4 l3 p
 mmfs_bank_scatter                               i  ii p4 l3 p
 mmfs_rmsnorm_supported                          i  i l

@@ -16,11 +16,13 @@ and the callers either side of the op:
     mmfs_amd.resampler   QKNormAttention: the Perceiver resampler's Q-Former attention with per-head q/k LayerNorm, fused
     mmfs_amd.llama_attn  LlamaSelfAttention, LlamaKVCache: the LLM's self-attention in text generation -- rotary embedding,
                          a key / value cache written in place (re-indexed, not copied, under beam search), prompt and single-token
-                         attention over it
+                         attention over it; in training, causal attention forward and backward with no L x L tensor
+                         (``llama_attn_train``, the module's training route)
 """
 from .functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch  # noqa: F401
 from .functions import QKNormAttentionFunction, qk_attn_supported  # noqa: F401
 from .functions import llama_attn_decode, llama_attn_prefill, llama_attn_supported, llama_rope_append, rope_table  # noqa: F401
+from .functions import LlamaAttnTrainFunction, llama_attn_train, llama_attn_train_supported  # noqa: F401
 from .levels import invalidate_caches  # noqa: F401
 from .llama_attn import LlamaKVCache, LlamaKVLayer, LlamaSelfAttention  # noqa: F401
 from .resampler import QKNormAttention  # noqa: F401

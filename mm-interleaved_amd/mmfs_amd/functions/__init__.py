@@ -9,3 +9,4 @@ from .pyramid_func import PyramidHeadFunction, pyramid_head_supported  # noqa: F
 from .sequence_func import ContextGatherFunction, SequenceEmbedFunction, sequence_supported  # noqa: F401,E402
 from .qk_attn_func import QKNormAttentionFunction, qk_attn_supported  # noqa: F401,E402
 from .llama_attn_func import llama_attn_decode, llama_attn_prefill, llama_attn_supported, llama_rope_append, rope_table  # noqa: F401,E402
+from .llama_train_func import LlamaAttnTrainFunction, llama_attn_train, llama_attn_train_supported  # noqa: F401,E402

@@ -23,7 +23,16 @@ handle and takes the framework route all the same (``last_reason`` says why) rea
 its new keys and values INTO the cache with framework ops and returns the handle, so ``cache.advance()`` counts the token on
 either route; a cache that cannot take them (another type, device or shape) raises.  Only ``use_cache=False`` appends nothing.
 ``module.route = "kernels"`` / ``"framework"`` forces either; a forced kernel route that does not apply raises.
+
+Training.  A module in training mode that is handed a 2-D ``attention_mask`` [B, q_len] and no ``past_key_value`` -- the
+convention of the reference's ``replace_llama_attn_with_flash_attn()``, whose ``_forward_train`` this is -- rotates q and k,
+runs CAUSAL attention, does not read the mask, ignores ``use_cache`` and returns ``(o_proj(context), None, None)``.  Device
+bf16 / fp16 tensors with heads of 128 channels outside autocast take csrc/mmfs_llama_train.hip forward and backward (no
+[B, H, L, L] tensor, bit-reproducible) from ``TRAIN_KERNEL_MIN_TOKENS`` tokens on; anything else states the same with
+framework ops, differentiable by autograd.  ``module.last_train`` says which ran.
 """
+import warnings
+
 import torch
 from torch import nn
 
@@ -33,11 +42,20 @@ DEFAULT_ROUTE = {"decode": "kernels", "prefill": "kernels"}
 # on the kernel route, a prompt of at least this many new tokens takes the prefill kernel behind the append, a shorter one
 # the framework ops on the cache's views (2: always; profiles/llama_attn.md holds the measurement behind it)
 PREFILL_KERNEL_MIN_TOKENS = 2
+# on the training route, a sequence of at least this many tokens takes the training kernels, a shorter one the framework ops
+# (1: always -- at B = 4, H = 32, bf16 the kernels' forward + backward took 145 / 324 / 2754 us against the framework
+# statement's 729 / 1074 / 10016 at L = 128 / 512 / 2048, more than both spreads apart at each: profiles/llama_attn.md, "Training")
+TRAIN_KERNEL_MIN_TOKENS = 1
 
 
 def _func():
     from .functions import llama_attn_func          # (loads the native library: host-only callers never need it)
     return llama_attn_func
+
+
+def _train_func():
+    from .functions import llama_train_func         # (loads the native library)
+    return llama_train_func
 
 
 def rope_table(head_dim, max_positions, base=10000, device=None):
@@ -202,6 +220,7 @@ class LlamaSelfAttention(nn.Module):
         self.last_reason = None                 # why it was the framework route
         self.prefill_kernel = None              # None: PREFILL_KERNEL_MIN_TOKENS decides; True / False: the prefill kernel / framework ops
         self.last_prefill = None                # "kernel" / "framework ops": what the last prompt on the kernel route took
+        self.last_train = None                  # "kernel" / "framework ops": what the last call on the training route took; else None
 
     def rope(self, device, positions=0):
         """(cos, sin) [>= positions, head_dim / 2] fp32 on ``device``; grown when a sequence is longer, as the reference's"""
@@ -258,6 +277,10 @@ class LlamaSelfAttention(nn.Module):
             raise ValueError(f"prefill_kernel: {self.prefill_kernel!r} is not None, True or False")
         rows, q_len = hidden_states.shape[0], hidden_states.shape[1]
         q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
+        self.last_train = None
+        if self.training and past_key_value is None and isinstance(attention_mask, torch.Tensor) and \
+                tuple(attention_mask.shape) == (rows, q_len):
+            return self._train(q, k, v, position_ids, output_attentions)
         reason = self._kernel_reason(hidden_states, q, attention_mask, past_key_value, output_attentions, use_cache)
         if reason is None and not forced and DEFAULT_ROUTE["decode" if q_len == 1 else "prefill"] != "kernels":
             reason = "the default route of this shape class"
@@ -271,6 +294,43 @@ class LlamaSelfAttention(nn.Module):
             return self._kernels(q, k, v, attention_mask, position_ids, past_key_value)
         self.last_route, self.last_reason = "framework", reason
         return self._framework(q, k, v, attention_mask, position_ids, past_key_value, output_attentions, use_cache)
+
+    # ------------------------------------------------------------------------------------------ the training route
+    def _train_reason(self, q):
+        """why this training call cannot take the kernels, or None"""
+        if q.dim() != 3 or not q.is_cuda:
+            return "host tensors"
+        if torch.is_autocast_enabled():
+            return "autocast"
+        if not _train_func().llama_attn_train_supported(q, self.num_heads):
+            return "tensors the kernels do not serve"
+        return None
+
+    def _train(self, q, k, v, position_ids, output_attentions):
+        """the reference's _forward_train: the mask is not read, the attention is causal, nothing is cached"""
+        if output_attentions:
+            warnings.warn("Output attentions is not supported for patched `LlamaAttention`, returning `None` instead.")
+        rows, q_len, _ = q.shape
+        reason = self._train_reason(q)
+        if reason is None and self.route is None and q_len < TRAIN_KERNEL_MIN_TOKENS:
+            reason = "fewer tokens than TRAIN_KERNEL_MIN_TOKENS"
+        if self.route == "kernels" and reason is not None:
+            raise RuntimeError(f"LlamaSelfAttention: route='kernels', but the call has {reason}")
+        if position_ids is None:
+            position_ids = torch.arange(q_len, device=q.device)[None, :].expand(rows, -1)
+        if reason is None and self.route != "framework":
+            self.last_route, self.last_reason, self.last_train = "kernels", None, "kernel"
+            capturing = torch.cuda.is_current_stream_capturing()
+            cos, sin = self.rope(q.device, 0 if capturing else q_len)
+            context = _train_func().llama_attn_train(q, k, v, position_ids, cos, sin, self.num_heads)
+            return self.o_proj(context), None, None
+        self.last_route, self.last_reason, self.last_train = "framework", reason, "framework ops"
+        cos, sin = (torch.cat((t, t), dim=-1).to(q.dtype)[position_ids].unsqueeze(1) for t in self.rope(q.device, q_len))
+        query, keys = self._split(q), self._split(k)
+        query = query * cos + rotate_half(query) * sin
+        keys = keys * cos + rotate_half(keys) * sin
+        context, _ = self._attend(query, keys, self._split(v), None, False, causal=True)
+        return self.o_proj(context), None, None
 
     # ------------------------------------------------------------------------------------------ the kernel route
     def _kernels(self, q, k, v, mask, position_ids, layer):
@@ -300,12 +360,15 @@ class LlamaSelfAttention(nn.Module):
         return self.o_proj(context), None, layer
 
     # ------------------------------------------------------------------------------------------ the framework route
-    def _attend(self, query, keys, values, mask, want_weights):
+    def _attend(self, query, keys, values, mask, want_weights, causal=False):
         """query [B, H, L, D] (rotated), keys / values [B, H, kv, D], mask broadcastable to [B, 1, L, kv] or None ->
         (context [B, L, H D], probabilities or None).  The reference's order of roundings: the query is scaled before the
         product, the sum with the mask is clamped at finfo.min, the softmax runs in fp32 (wider types keep theirs) and
-        is rounded back before the second product."""
+        is rounded back before the second product.  ``causal``: key t > query j is filled with -Inf (the training route)."""
         scores = (query * self.head_dim ** -0.5) @ keys.transpose(-1, -2)
+        if causal:
+            future = torch.ones(scores.shape[-2:], dtype=torch.bool, device=scores.device).triu(1)
+            scores = scores.masked_fill(future, float("-inf"))
         if mask is not None:
             scores = (scores + mask).clamp_min(torch.finfo(scores.dtype).min)
         probs = scores.softmax(dim=-1, dtype=torch.promote_types(scores.dtype, torch.float32)).to(query.dtype)
