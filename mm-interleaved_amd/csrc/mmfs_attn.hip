@@ -52,8 +52,10 @@
 //                              VGPRs  AGPRs  LDS bytes  waves / SIMD
 //   qk_attn_fwd  qk-norm        120    32     37120      3
 //   qk_attn_fwd  plain          112    32     37120      3
-//   qk_attn_bwd  qk-norm        201    68     125184     1
-//   qk_attn_bwd  plain          120    64     119552     1
+//   qk_attn_bwd  qk-norm fp16   201    68     125184     1
+//   qk_attn_bwd  qk-norm bf16   203    64     125184     1
+//   qk_attn_bwd  plain   fp16   120    64     119552     1
+//   qk_attn_bwd  plain   bf16   124    64     119552     1
 //   qk_attn_params              5      0      0          8
 // The backward's workgroup holds the whole query side of its (b, h) in LDS: one workgroup per CU, one wave per SIMD.
 //
@@ -88,6 +90,7 @@
 // Offsets are 64-bit.
 #include "mmfs_attn_core.h"
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace mmfs {
 
@@ -338,6 +341,14 @@ qk_attn_bwd(const T *__restrict__ q, const T *__restrict__ k, const T *__restric
         const int kl = wave * 16 + c, key = k0 + kl;                // this lane's key
         const bool key_ok = key < Nk;
         const float bias_c = sBias[kl];
+        // bf16: a key whose bias lies far below the row maxima has weights at or below fp32's smallest normal, where
+        // v_exp_f32 returns 0; its column of P and dS is carried times 2^-ex (ex <= 0, an exact power of two, 0 for every
+        // key within 22 of the maxima: the same bits as without it) and dv, dk and the stored dS are scaled back by ldexp.
+        // p <= 1 keeps the scaled weight at or below 2^64.  fp16 has no such weights (they are 0 in T) and no such range.
+        float ex = 0.f;
+        if constexpr (std::is_same<T, bf16_t>::value)
+            ex = fminf(0.f, fmaxf(-64.f, rintf((bias_c - sM[0]) * kLog2e) + 32.f));
+        const int exi = (int)ex;
         s16x8 fk[2], fv[2];
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
@@ -362,10 +373,10 @@ qk_attn_bwd(const T *__restrict__ q, const T *__restrict__ k, const T *__restric
                 for (int r = 0; r < 4; ++r) {
                     const int qi = q0 + 4 * g + r;
                     const float x = score_of<T, kD>(s[r], bias_c);
-                    const float pr = key_ok && qi < Nq ? exp_hw(x - sM[qi]) * sRl[qi] : 0.f;
+                    const float pr = key_ok && qi < Nq ? __builtin_amdgcn_exp2f((x - sM[qi]) * kLog2e - ex) * sRl[qi] : 0.f;
                     p[hf][r] = pr;
                     ds[hf][r] = key_ok && qi < Nq ? pr * (dp[r] - sDelta[qi]) : 0.f;
-                    sS[qi * kLd + kl] = bits_of<T>(ds[hf][r]);
+                    sS[qi * kLd + kl] = bits_of<T>(ldexpf(ds[hf][r], exi));
                 }
             }
             const s16x8 fp = pack_pair<T>(p[0], p[1]), fds = pack_pair<T>(ds[0], ds[1]);
@@ -385,11 +396,12 @@ qk_attn_bwd(const T *__restrict__ q, const T *__restrict__ k, const T *__restric
             for (int db = 0; db < 4; ++db) {
                 const int d0 = db * 16 + 4 * g;
                 if (key_ok) {
-                    const float o[4] = {dvt[db][0], dvt[db][1], dvt[db][2], dvt[db][3]};
+                    const float o[4] = {ldexpf(dvt[db][0], exi), ldexpf(dvt[db][1], exi), ldexpf(dvt[db][2], exi),
+                                        ldexpf(dvt[db][3], exi)};
                     store4<T>(dv + row + d0, o);
                 }
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dy[db][r] = dkt[db][r] * kScale;
+                for (int r = 0; r < 4; ++r) dy[db][r] = ldexpf(dkt[db][r] * kScale, exi);
                 if constexpr (NORM) {
                     float x[4] = {0.f, 0.f, 0.f, 0.f};
                     if (key_ok) load4<T>(k + row + d0, x);

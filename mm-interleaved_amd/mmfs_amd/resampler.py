@@ -154,9 +154,21 @@ class QKNormAttention(nn.Module):
             if self.position_embedding_type == "relative_key_query":
                 scores = scores + torch.einsum("bhrd,lrd->bhlr", key_layer, table)
         scores = scores / math.sqrt(self.attention_head_size)
-        if mask is not None:
-            scores = scores + mask
-        probs = scores.softmax(dim=-1)
+        if mask is not None and scores.dtype in (torch.bfloat16, torch.float16):
+            # A 16-bit sum would round score + bias to the bias's grid (a grid of 1 at a bias of 150 in bf16) and lose the
+            # score: the bias is added and the softmax taken in fp32, and the weights are rounded to T once.  With HF's masks
+            # (0 and finfo(T).min) these are the sum in T's own bits: score + 0 is the score, and a key at or below
+            # finfo(T).min keeps the mask entry as its score, which is what the sum in T leaves of it and the kernels' rule
+            # (csrc/mmfs_attn_core.h, score_of).
+            # (The masked branch adds score - score.detach(), an exact 0: the gradient passes through a masked key's
+            # score as it does through the sum in T.)
+            wide, s32 = mask.float(), scores.float()
+            scores = torch.where(wide <= torch.finfo(scores.dtype).min, wide + (s32 - s32.detach()), s32 + wide)
+            probs = scores.softmax(dim=-1).to(query_layer.dtype)
+        else:
+            if mask is not None:
+                scores = scores + mask
+            probs = scores.softmax(dim=-1)
         if cross and self.save_attention:
             self.save_attention_map(probs)
             probs.register_hook(self.save_attn_gradients)

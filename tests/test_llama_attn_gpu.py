@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 import torch
 
+from attn_score_families import CACHE_FAMILIES, decode_case
 from front_end_refs import worst
 from helpers import load_golden, poison_allocations
 from llama_attn_refs import attend64, linear64, rope64
+from llama_train_refs import row_error
 
 import mmfs_amd
 from mmfs_amd.llama_attn import LlamaKVCache, LlamaSelfAttention, rotate_half
@@ -232,6 +234,38 @@ def test_a_row_of_minus_infinity_is_nan_as_the_framework_s(dtype, monkeypatch):
     keys, values = cache.store[0, 0, 1:, :, :kv], cache.store[0, 1, 1:, :, :kv]
     r = attend64(q_rot[1:], keys, values, H, mask=mask[1:], dtype=dtype)
     hold("kernels", "context", ctx[1:], r["context"], r["E_context"], [])
+
+
+# ------------------------------------------------------------------ peaked, drifting and sink rows
+@pytest.mark.parametrize("dtype", DTYPES, **ids)
+@pytest.mark.parametrize("name", CACHE_FAMILIES, ids=lambda n: n.replace(" ", "_"))
+def test_decode_holds_the_bounds_and_the_row_measure_at_partial_maxima_far_apart(name, dtype, monkeypatch):
+    """kv = 2 SPLIT_KEYS + 1 at position 0 (tests/attn_score_families.py): the waves' and the splits' partial maxima lie up to 45
+    apart (``rising``, ``falling``), or one key of the first and of the middle split holds the weight (``sink``); then plain
+    unit-normal keys under an fp32 bias that rises by 0.25 a key.  Beside the per-element bounds, which admit half of p at
+    |s| = 40 in bf16, the kernel's context is held row by row to 8 u of the row's norm (llama_train_refs.row_error;
+    tests/test_attn_families.py: a host model of the kernel's roundings measures 0.06, partials merged without exp(m_j - M) 24
+    or more)."""
+    poison_allocations(monkeypatch)
+    report, rows = [], {}
+    for tag, case in ((" " + name, decode_case(name, dtype, SPLIT_KEYS)), (" rising bias", decode_case("bias", dtype, SPLIT_KEYS))):
+        keys, values = case["keys"], case["values"]
+        kv = keys.shape[2]
+        assert kv == 2 * SPLIT_KEYS + 1 and keys.shape[:2] == (B, H)
+        cache = LlamaKVCache(1, B, H, kv + 3, 128, dtype, DEV)
+        cache.store.fill_(float("nan"))
+        cache.store[0, 0, :, :, :kv - 1] = keys[:, :, :kv - 1].to(DEV)
+        cache.store[0, 1, :, :, :kv - 1] = values[:, :, :kv - 1].to(DEV)
+        cache.set_length(kv - 1)
+        pos = torch.zeros(B, 1, dtype=torch.long, device=DEV)
+        mask = None if case["bias"] is None else case["bias"].to(DEV)
+        ctx, r = decode_both_routes(cache, case["q"].to(DEV), case["k"].to(DEV), case["v"].to(DEV), pos, mask, report, tag)
+        # position 0 rotates nothing: the cache holds the host's rows, bit for bit
+        assert torch.equal(cache.store[0, 0, :, :, :kv].cpu(), keys) and torch.equal(cache.store[0, 1, :, :, :kv].cpu(), values)
+        rows[tag] = row_error(ctx, r["context"], dtype)
+    show(report)
+    print("worst row error / (8 u (|row| + floor)), kernels:" + ",".join(f"{t} {x:.3f}" for t, x in rows.items()))
+    assert max(rows.values()) <= 1.0, rows
 
 
 # ------------------------------------------------------------------ the reference's fixtures through the module

@@ -13,9 +13,11 @@ import types
 import pytest
 import torch
 
+from attn_score_families import CACHE_FAMILIES, prefill_case
 from front_end_refs import worst
 from helpers import poison_allocations
 from llama_attn_refs import attend64
+from llama_train_refs import row_error
 from llama_prefill_refs import clamped, hf_mask, left_padded, padding_row
 
 import mmfs_amd
@@ -217,6 +219,51 @@ def test_the_causal_flag_is_the_materialised_mask_and_skipping_moves_no_bit(case
         b = prefill(cache, q_rot, bias, causal, visit_all=True)
         assert torch.equal(a.view(torch.int16), b.view(torch.int16)), (causal, None if bias is None else tuple(bias.shape))
     assert torch.equal(flagged.view(torch.int16), prefill(cache, q_rot, row, True, visit_all=True).view(torch.int16))
+
+
+# ------------------------------------------------------------------ peaked, drifting and sink rows
+@pytest.mark.parametrize("dtype", DTYPES, **ids)
+@pytest.mark.parametrize("name", CACHE_FAMILIES, ids=lambda n: n.replace(" ", "_"))
+def test_prefill_holds_the_bounds_and_the_row_measure_at_drifting_and_sink_rows(name, dtype, monkeypatch):
+    """held = K + 1, Lq = 2 G + 1, the family over the held and the appended keys, appended at position 0
+    (tests/attn_score_families.py): the running maximum rises at every key tile, or later tiles underflow, or one key holds
+    the weight.  No mask, and the padding row with the causal flag; skipping tiles moves no bit.  Beside the per-element
+    bounds the kernel's context is held row by row to 8 u of the row's norm (llama_train_refs.row_error;
+    tests/test_attn_families.py: a host model of the kernel's roundings measures 0.1)."""
+    case = prefill_case(name, dtype, PREFILL_TILES)
+    held, Lq = case["held"], case["Lq"]
+    n = held + Lq
+    assert (held, Lq) == (K + 1, 2 * G + 1)
+    cache = LlamaKVCache(1, B, H, cap_of(n), 128, dtype, DEV)
+    cache.store.fill_(float("nan"))
+    cache.store[0, 0, :, :, :held] = case["keys"][:, :, :held].to(DEV)
+    cache.store[0, 1, :, :, :held] = case["values"][:, :, :held].to(DEV)
+    cache.set_length(held)
+    cos, sin = tables()
+    pos = torch.zeros(B, Lq, dtype=torch.long, device=DEV)
+    q_rot = mmfs_amd.llama_rope_append(case["q"].to(DEV), case["k"].to(DEV), case["v"].to(DEV), pos, cos, sin, cache[0].keys,
+                                       cache[0].values, cache.length, cache.src_row)
+    keys, values = logical(cache, n)
+    # position 0 rotates nothing: q_rot and the cache hold the host's rows, bit for bit
+    assert torch.equal(q_rot.cpu(), case["q"]) and torch.equal(keys.cpu(), case["keys"]) and torch.equal(values.cpu(), case["values"])
+    masks = masks_of(held, Lq, dtype)
+    poison_allocations(monkeypatch)
+    report, rows = [], {}
+    for kind in ("none", "row + causal"):
+        bias, causal, full = masks[kind]
+        r = attend64(q_rot, keys, values, H, mask=clamped(full, dtype), dtype=dtype)
+        ctx = prefill(cache, q_rot, bias, causal)
+        hold(f"kernel {name} {kind}", ctx, r["context"], r["E_context"], report)
+        rows[kind] = row_error(ctx, r["context"], dtype)
+        if kind == "none":
+            fw = module(H, dtype)._attend(q_rot.view(B, Lq, H, 128).transpose(1, 2), keys, values, None, False)[0]
+            hold(f"framework {name} {kind}", fw, r["context"], r["E_context"], report)
+        a = prefill(cache, q_rot, bias, causal, visit_all=False)
+        b = prefill(cache, q_rot, bias, causal, visit_all=True)
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16)) and torch.equal(a.view(torch.int16), ctx.view(torch.int16)), kind
+    show(report)
+    print(f"worst row error / (8 u (|row| + floor)), kernel {name}: " + ", ".join(f"{t} {x:.3f}" for t, x in rows.items()))
+    assert max(rows.values()) <= 1.0, rows
 
 
 # ------------------------------------------------------------------ the cache is read only; indirection; graphs

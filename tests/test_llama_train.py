@@ -150,12 +150,12 @@ def test_the_bounds_hold_the_framework_statement_and_refuse_four_defects(dtype):
 
 
 # ------------------------------------------------------------------ the tight check at the GPU tests' own inputs
-def kernel_model(q, k, v, do, pos, cos, sin, dtype):
+def kernel_model(q, k, v, do, pos, cos, sin, dtype, heads=None):
     """The kernels' rounding points on the host: fp64 arithmetic, q_rot, k_rot, P and dS rounded to T where they enter a
     product, every output rounded once -> (context, dq, dk, dv) in T."""
     rt = lambda x: x.to(dtype).double()
     c, s = (torch.cat((t, t), dim=-1).double()[pos].unsqueeze(1) for t in (cos, sin))
-    split = lambda x: x.double().unflatten(-1, (H_GPU, 128)).transpose(1, 2)
+    split = lambda x: x.double().unflatten(-1, (heads or H_GPU, 128)).transpose(1, 2)
     merge = lambda x: x.transpose(1, 2).flatten(2).to(dtype)
     qh, kh, vh, g = split(q), split(k), split(v), split(do)
     qr, kr = rt(qh * c + rotate_half(qh) * s), rt(kh * c + rotate_half(kh) * s)

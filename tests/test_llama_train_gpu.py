@@ -8,6 +8,10 @@ that the framework's statement meets them and four defective ones do not), and t
 by row to a tight relative measure (``row_error``; the same file shows, at exactly these inputs, the defects it refuses).  Outputs are poisoned before the kernels run:
 an element nobody wrote is NaN.
 
+Peaked, drifting and sink score rows (tests/attn_score_families.py; tests/test_attn_families.py shows on the host what they
+catch that unit-normal rows let pass), a walk over nine query tiles, positions outside the rotary table and the backward's
+linearity in dO follow the unit-normal tests.
+
 Worst bound ratios measured on an MI355X are kept in profiles/llama_attn.md, "Training"."""
 import types
 
@@ -16,6 +20,7 @@ import torch
 from torch import nn
 from torch.utils.checkpoint import checkpoint
 
+from attn_score_families import TRAIN_FAMILIES, WALK_FAMILY, train_inputs
 from helpers import poison_allocations
 from llama_train_refs import draw as refs_draw, tight_ratios, train64, worst
 
@@ -55,16 +60,16 @@ def draw(seed, L, dtype, B=B, H=H, first=5):
 _tables = {}
 
 
-def tables():
-    if "t" not in _tables:
-        _tables["t"] = rope_table(128, MAX_POS, device=DEV)
-    return _tables["t"]
+def tables(max_pos=MAX_POS):
+    if max_pos not in _tables:
+        _tables[max_pos] = rope_table(128, max_pos, device=DEV)
+    return _tables[max_pos]
 
 
-def run_abi(q, k, v, up, pos, heads=H):
+def run_abi(q, k, v, up, pos, heads=H, max_pos=MAX_POS):
     """the three entries one after the other, as the Function calls them"""
     f = func()
-    cos, sin = tables()
+    cos, sin = tables(max_pos)
     q_rot, k_rot = f.train_rope(q, k, pos, cos, sin, heads)
     ctx, lse = f.train_forward(q_rot, k_rot, v, heads)
     dq, dk, dv = f.train_backward(q_rot, k_rot, v, ctx, up, lse, pos, cos, sin, heads)
@@ -72,8 +77,8 @@ def run_abi(q, k, v, up, pos, heads=H):
     return dict(zip(NAMES, (q_rot, k_rot, ctx, lse, dq, dk, dv)))
 
 
-def run_function(q, k, v, up, pos, heads=H):
-    cos, sin = tables()
+def run_function(q, k, v, up, pos, heads=H, max_pos=MAX_POS):
+    cos, sin = tables(max_pos)
     leaves = [t.clone().requires_grad_(True) for t in (q, k, v)]
     ctx = mmfs_amd.llama_attn_train(*leaves, pos, cos, sin, heads)
     grads = torch.autograd.grad(ctx, leaves, up)
@@ -252,3 +257,103 @@ def test_a_checkpointed_call_gives_the_same_gradients():
     assert m.last_train == "kernel"
     for n in plain:
         assert torch.equal(plain[n], again[n]), n
+
+
+# ------------------------------------------------------------------ peaked, drifting and sink rows; the long walk
+FB, FH, FSEED = 1, 2, 5                                 # tests/test_attn_families.py's: the host model is held at these very inputs
+WALK_MAX_POS = 2048
+
+
+def family_length():
+    Q, K = func().TRAIN_TILES[:2]
+    return 2 * Q + K // 2 + 3
+
+
+def walk_length():
+    Q, K = func().TRAIN_TILES[:2]
+    return 8 * Q + K + 5
+
+
+def hold_both_measures(name, L, dtype, monkeypatch, max_pos=MAX_POS):
+    q, k, v, up, pos = train_inputs(name, FSEED, L, dtype, FB, FH, device=DEV)
+    assert 0 <= int(pos.min()) and int(pos.max()) < max_pos
+    cos, sin = tables(max_pos)
+    ref = train64(q, k, v, pos, cos.cpu(), sin.cpu(), FH, dtype, upstream=up)
+    poison_allocations(monkeypatch)
+    abi = run_abi(q, k, v, up, pos, FH, max_pos)
+    fn = run_function(q, k, v, up, pos, FH, max_pos)
+    ratios = {n: worst(abi[n], ref[n], ref["E_" + n]) for n in NAMES}
+    tight = tight_ratios(abi, ref, dtype)
+    print(f"{name} L {L} {dtype}: lse {float(ref['lse'].min()):.1f} .. {float(ref['lse'].max()):.1f}; worst |got - ref| / bound " +
+          ", ".join(f"{n} {x:.3f}" for n, x in ratios.items()))
+    print(f"{name} L {L} {dtype}: worst row error / (8 u (|row| + share + floor)) " + ", ".join(f"{n} {x:.3f}" for n, x in tight.items()))
+    assert max(ratios.values()) <= 1.0, ratios
+    assert max(tight.values()) <= 1.0, tight
+    for n in fn:                                                            # the Function is the three entries
+        assert torch.equal(fn[n], abi[n]), n
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+@pytest.mark.parametrize("name", TRAIN_FAMILIES, ids=lambda n: n.replace(" ", "_"))
+def test_peaked_drifting_and_sink_rows_hold_both_measures(name, dtype, monkeypatch):
+    """every position 0, where the rotation is exact: a running maximum that rises by 19 or more a key tile and
+    scores above 88.7 (``rising``), whole key tiles that underflow behind an early maximum (``falling``), one key with most of
+    a row's weight (``sink``); lse reaches 105, so the backward's exp((K q^T - lse sqrt(128)) / sqrt(128)) starts its
+    accumulators near -1190"""
+    hold_both_measures(name, family_length(), dtype, monkeypatch)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+@pytest.mark.parametrize("name", [WALK_FAMILY, "plain"], ids=lambda n: n.replace(" ", "_"))
+def test_a_walk_over_nine_query_tiles_holds_both_measures(name, dtype, monkeypatch):
+    """L = 8 Q + K + 5: the rising family at position 0 and the plain draw at real positions 5 .. L + 4"""
+    hold_both_measures(name, walk_length(), dtype, monkeypatch, WALK_MAX_POS)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+def test_a_position_outside_the_table_is_nan_from_that_token_on_and_nowhere_else(dtype, monkeypatch):
+    """One token t of batch row 0 at position -1, MAX_POS or 2^40.  The expectation is the kernels' contract, not train64's:
+    its matrix products turn 0 x NaN into NaN where the kernels select."""
+    Q, K = func().TRAIN_TILES[:2]
+    L = family_length()
+    q, k, v, up, pos = draw(29, L, dtype, B=2, H=FH)
+    poison_allocations(monkeypatch)
+    clean = run_abi(q, k, v, up, pos, FH)
+    assert all(bool(torch.isfinite(clean[n]).all()) for n in NAMES)
+    for t in (0, K + 5, L - 1):
+        for bad in (-1, MAX_POS, 1 << 40):
+            pos2 = pos.clone()
+            pos2[0, t] = bad
+            got = run_abi(q, k, v, up, pos2, FH)
+            where = (t, bad)
+            for n in NAMES:                                                 # the other batch row
+                assert torch.equal(got[n][1], clean[n][1]), (n, where)
+            others = torch.arange(L, device=DEV) != t
+            for n in ("q_rot", "k_rot"):
+                assert bool(torch.isnan(got[n][0, t]).all()), (n, where)
+                assert torch.equal(got[n][0, others], clean[n][0, others]), (n, where)
+            for n in ("context", "dq"):
+                assert torch.equal(got[n][0, :t], clean[n][0, :t]), (n, where)
+                assert bool(torch.isnan(got[n][0, t:]).all()), (n, where)
+            assert torch.equal(got["lse"][0, :, :t], clean["lse"][0, :, :t]), where
+            for n in ("dk", "dv"):
+                assert bool(torch.isnan(got[n][0]).all()), (n, where)
+
+
+@pytest.mark.parametrize("name", ["plain", TRAIN_FAMILIES[0]], ids=lambda n: n.replace(" ", "_"))
+def test_the_backward_is_linear_in_the_upstream_gradient_and_the_forward_in_v(name, monkeypatch):
+    """bf16: backward(2^k dO) is 2^k backward(dO) and the context of 2^k v is 2^k times the context, bit for bit, for k = -20 and
+    +20 (a power of two moves no significand, and bf16's exponent range is fp32's).  Not in fp16: at dO 2^-10 dS is subnormal
+    there, and a host model of the kernels' roundings misses dk by 1.35 of the tight measure."""
+    dtype = torch.bfloat16
+    q, k, v, up, pos = train_inputs(name, FSEED, family_length(), dtype, FB, FH, device=DEV)
+    poison_allocations(monkeypatch)
+    clean = run_abi(q, k, v, up, pos, FH)
+    for e in (-20, 20):
+        scaled = lambda t: (t.float() * 2.0 ** e).to(dtype)
+        got = run_abi(q, k, v, scaled(up), pos, FH)
+        for n in ("dq", "dk", "dv"):
+            assert bool(torch.isfinite(got[n]).all()) and torch.equal(got[n], scaled(clean[n])), (n, e)
+        assert torch.equal(got["context"], clean["context"]) and torch.equal(got["lse"], clean["lse"]), e
+        wide = run_abi(q, k, scaled(v), up, pos, FH)
+        assert torch.equal(wide["context"], scaled(clean["context"])) and torch.equal(wide["lse"], clean["lse"]), e

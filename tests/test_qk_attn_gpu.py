@@ -203,6 +203,60 @@ def test_keys_at_minus_infinity_are_nan_exactly_where_the_framework_route_has_na
     show(report)
 
 
+# ------------------------------------------------------------------ large scores
+def large_bias(kind, B, Nk, dtype):
+    """q and k are normalised, so a large part of a score can only come through the key bias: an fp32 row that rises or falls
+    by 0.5 a key (a running maximum that rises at every key tile; tiles that underflow behind the first), or one key at +8;
+    at values T holds, since the framework route casts the bias to T"""
+    t = torch.arange(Nk, dtype=torch.float32)
+    row = {"rise": 0.5 * t, "fall": -0.5 * t, "peak": torch.zeros(Nk).index_fill_(0, torch.tensor([Nk // 2]), 8.0)}[kind]
+    return row.to(dtype).float()[None].expand(B, -1).contiguous().to(DEV)
+
+
+LARGE = [SHAPES[4], max(SHAPES, key=lambda s: s[0] * s[1])]
+assert LARGE[0][:2] == (64, 64)
+
+
+def large_case(shape, kind, dtype):
+    Nq, Nk, norm, _ = shape
+    gen = torch.Generator().manual_seed(1000 * Nq + Nk + 7)
+    q, k, v, up, params, _ = draw(gen, 2, Nq, Nk, 3, dtype, norm, False)
+    return q, k, v, up, params, large_bias(kind, 2, Nk, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+@pytest.mark.parametrize("kind", ["rise", "fall", "peak"])
+@pytest.mark.parametrize("shape", LARGE, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_kernels_hold_the_bounds_at_large_key_biases(shape, kind, dtype, monkeypatch):
+    """Forward and backward against attention64; lse reaches 153 at the rising bias over 300 keys.  In bf16 at (128, 300) one
+    key's bias lies 88.5 below the largest: its weights sit at 2^-126, where the hardware exp2 returns 0; qk_attn_bwd carries
+    such a key's column of P and dS times a power of two (profiles/qk_attn.md: dv measured 2.86 and 3.09 before that)."""
+    q, k, v, up, params, kb = large_case(shape, kind, dtype)
+    r = attention64(q, k, v, 3, norm=params, eps=EPS, bias=kb, upstream=up, dtype=dtype)
+    poison_allocations(monkeypatch)
+    report = []
+    hold("kernels", run_kernels(q, k, v, up, params, kb, 3), r, report)
+    print(f"{kind} lse {float(r['lse'].min()):.1f} .. {float(r['lse'].max()):.1f}")
+    show(report)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+@pytest.mark.parametrize("kind", ["rise", "fall", "peak"])
+@pytest.mark.parametrize("shape", LARGE, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_framework_route_holds_the_bounds_at_large_key_biases(shape, kind, dtype, monkeypatch):
+    """The framework route under the same bounds.  With a mask in 16-bit storage it adds the bias and takes the softmax in
+    fp32 (a sum in T rounds score + 150 to a grid of 1 in bf16, which E_s = .. + 3 u |s0| does not count: the context measured
+    up to 13.5 that way, profiles/qk_attn.md)."""
+    q, k, v, up, params, kb = large_case(shape, kind, dtype)
+    r = attention64(q, k, v, 3, norm=params, eps=EPS, bias=kb, upstream=up, dtype=dtype)
+    poison_allocations(monkeypatch)
+    report = []
+    try:
+        hold("framework", run_framework(q, k, v, up, params, kb, 3), r, report)
+    finally:
+        show(report)
+
+
 # ------------------------------------------------------------------ the reference's fixtures
 @pytest.mark.parametrize("case", ["self_qknorm", "cross_qknorm_masked", "cross_plain_77", "cross_one_key_left"])
 def test_goldens_at_bf16(case, monkeypatch):
