@@ -528,11 +528,8 @@ bool supported(int dtype, int64_t D, int64_t Nq, int64_t Nk)
 
 int check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Nq, int64_t Nk)
 {
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
-    if (B < 0 || H < 0 || D < 0 || Nq < 0 || Nk < 0) return MMFS_E_DIMS;
-    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
-    if (!supported(dtype, D, Nq, Nk)) return MMFS_E_UNSUPPORTED;
-    return MMFS_OK;
+    if (const int rc = batch_heads_check(dtype, B, H, D, Nq, Nk)) return rc;
+    return supported(dtype, D, Nq, Nk) ? MMFS_OK : MMFS_E_UNSUPPORTED;
 }
 
 // the four LayerNorm pointers: all or none
@@ -567,12 +564,10 @@ int qk_attn_check(int dtype, const void *q, const void *k, const void *v, const 
     a.bias_f32 = key_bias ? small_f32(bias_dtype, dtype) : 1;
     if (a.norm_f32 < 0 || a.bias_f32 < 0) return MMFS_E_DTYPE;
     if (key_bias && bias_stride != 0 && bias_stride != Nk) return MMFS_E_DIMS;
-    if (B * H && (!q || !k || !v)) return MMFS_E_NULLPTR;
-    const uintptr_t small = (uintptr_t)qw | (uintptr_t)qb | (uintptr_t)kw | (uintptr_t)kb;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || !small_aligned(small, a.norm_f32) ||
-        !small_aligned((uintptr_t)key_bias, a.bias_f32))
-        return MMFS_E_ALIGN;
-    return MMFS_OK;
+    const bool any = B * H != 0;
+    const int na = a.norm_f32 ? 4 : 2, ba = a.bias_f32 ? 4 : 2;
+    return check_tensors({{q, 16, any}, {k, 16, any}, {v, 16, any}, maybe(qw, na), maybe(qb, na), maybe(kw, na), maybe(kb, na),
+                          maybe(key_bias, ba)});
 }
 
 }  // namespace
@@ -588,8 +583,7 @@ int mmfs_qk_attn_forward(int dtype, const void *q, const void *k, const void *v,
                                  bias_dtype, bias_stride, B, H, D, Nq, Nk, a);
     if (rc) return rc;
     if (B * H == 0) return MMFS_OK;
-    if (!context || !lse || !stats) return MMFS_E_NULLPTR;
-    if ((uintptr_t)context % 16 || ((uintptr_t)lse | (uintptr_t)stats) % 4) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{context, 16}, {lse, 4}, {stats, 4}})) return rt;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         auto kernel = a.norm ? qk_attn_fwd<T, true> : qk_attn_fwd<T, false>;
@@ -612,18 +606,15 @@ int mmfs_qk_attn_backward(int dtype, const void *q, const void *k, const void *v
     const int rc = qk_attn_check(dtype, q, k, v, q_norm_weight, q_norm_bias, k_norm_weight, k_norm_bias, norm_dtype, key_bias,
                                  bias_dtype, bias_stride, B, H, D, Nq, Nk, a);
     if (rc) return rc;
-    if (a.norm && (!partials || !grad_params)) return MMFS_E_NULLPTR;
-    if (((uintptr_t)partials | (uintptr_t)grad_params) % 4) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{partials, 4, a.norm != 0}, {grad_params, 4, a.norm != 0}})) return rt;
     if (B * H == 0) {
         // no workgroup: the parameter gradients are the empty sum
         if (!a.norm) return MMFS_OK;
         hipLaunchKernelGGL(qk_attn_params, dim3(1), dim3(4 * kD), 0, (hipStream_t)stream, partials, grad_params, 0);
         return (int)hipGetLastError();
     }
-    if (!context || !grad_context || !stats || !grad_q || !grad_k || !grad_v) return MMFS_E_NULLPTR;
-    if (((uintptr_t)context | (uintptr_t)grad_context | (uintptr_t)grad_q | (uintptr_t)grad_k | (uintptr_t)grad_v) % 16 ||
-        (uintptr_t)stats % 4)
-        return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{context, 16}, {grad_context, 16}, {stats, 4}, {grad_q, 16}, {grad_k, 16}, {grad_v, 16}}))
+        return rt;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         auto kernel = a.norm ? qk_attn_bwd<T, true> : qk_attn_bwd<T, false>;

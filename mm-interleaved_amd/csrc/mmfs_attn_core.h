@@ -70,9 +70,17 @@ template <typename T> __device__ __forceinline__ void store4(T *p, const float (
 
 // ---- host side: what the entries check alike
 
-// the type of a small fp32-or-T vector (LayerNorm parameters, a bias): 1 fp32, 0 T, < 0 neither; and its alignment
+// the type of a small fp32-or-T vector (LayerNorm parameters, a bias): 1 fp32, 0 T, < 0 neither (it is aligned to 4 or 2 bytes)
 inline int small_f32(int small_dtype, int dtype) { return small_dtype == MMFS_F32 ? 1 : small_dtype == dtype ? 0 : -1; }
-inline bool small_aligned(uintptr_t p, int f32) { return p % (f32 ? 4 : 2) == 0; }
+
+// what every attention entry asks of its dtype code, batch and heads; of its other dimensions (a, b, c) only the sign
+inline int batch_heads_check(int dtype, int64_t B, int64_t H, int64_t a, int64_t b, int64_t c)
+{
+    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
+    if (B < 0 || H < 0 || a < 0 || b < 0 || c < 0) return MMFS_E_DIMS;
+    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
+    return MMFS_OK;
+}
 
 // the LLaMA entries (decode, prefill, the append): a cache [B, H, cap, 128], Lq new tokens a row
 constexpr int kLlamaD = 128;
@@ -85,11 +93,8 @@ inline bool llama_supported(int dtype, int64_t D, int64_t Lq, int64_t cap)
 
 inline int llama_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lq, int64_t cap)
 {
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
-    if (B < 0 || H < 0 || D < 0 || Lq < 0 || cap < 0) return MMFS_E_DIMS;
-    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
-    if (!llama_supported(dtype, D, Lq, cap)) return MMFS_E_UNSUPPORTED;
-    return MMFS_OK;
+    if (const int rc = batch_heads_check(dtype, B, H, D, Lq, cap)) return rc;
+    return llama_supported(dtype, D, Lq, cap) ? MMFS_OK : MMFS_E_UNSUPPORTED;
 }
 
 // the training entries (mmfs_llama_train.hip): no cache, L tokens a row; an empty problem (B, H or L of 0) is no error
@@ -102,11 +107,8 @@ inline bool llama_train_supported(int dtype, int64_t D, int64_t L)
 
 inline int llama_train_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t L)
 {
-    if (dtype != MMFS_F32 && dtype != MMFS_F16 && dtype != MMFS_BF16 && dtype != MMFS_F64) return MMFS_E_DTYPE;
-    if (B < 0 || H < 0 || D < 0 || L < 0) return MMFS_E_DIMS;
-    if (B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
-    if (!llama_train_supported(dtype, D, L ? L : 1)) return MMFS_E_UNSUPPORTED;
-    return MMFS_OK;
+    if (const int rc = batch_heads_check(dtype, B, H, D, L, 0)) return rc;
+    return llama_train_supported(dtype, D, L ? L : 1) ? MMFS_OK : MMFS_E_UNSUPPORTED;
 }
 
 // their bias argument: -> status and the type flag (fp32 without a bias); the strides are the entry's own to judge

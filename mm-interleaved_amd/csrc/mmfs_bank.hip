@@ -235,18 +235,17 @@ int mmfs_bank_gather(int dtype, int n_levels, const void *const *level_ptrs, con
     const int rc = make_levels(n_levels, const_cast<void *const *>(level_ptrs), level_hw, &L);
     if (rc) return rc;
     if (n_slots == 0 || C == 0) return MMFS_OK;
-    if (!src_index || !bank) return MMFS_E_NULLPTR;
     const int es = mmfs::elem_size(dtype);
-    if (((uintptr_t)bank % es)) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{src_index, 1}, {bank, es}})) return rt;
     const int c_tiles = (int)((C + kTile - 1) / kTile);
     if ((int64_t)L.tiles * c_tiles > 0x7fffffffLL) return MMFS_E_DIMS;
     const dim3 grid((unsigned)(L.tiles * c_tiles), (unsigned)n_slots);
     hipStream_t st = (hipStream_t)stream;
-    if (es == 4)
-        hipLaunchKernelGGL((bank_gather_kernel<4>), grid, dim3(kBankThreads), 0, st, L, src_index, bank, (int)C, n_img, c_tiles);
-    else
-        hipLaunchKernelGGL((bank_gather_kernel<2>), grid, dim3(kBankThreads), 0, st, L, src_index, bank, (int)C, n_img, c_tiles);
-    return (int)hipGetLastError();
+    return by_int<4, 2>(es, [&](auto tag) {
+        hipLaunchKernelGGL((bank_gather_kernel<decltype(tag)::value>), grid, dim3(kBankThreads), 0, st, L, src_index, bank, (int)C,
+                           n_img, c_tiles);
+        return (int)hipGetLastError();
+    });
 }
 
 int mmfs_bank_scatter(int dtype, int n_levels, void *const *grad_level_ptrs, const int64_t *level_hw,
@@ -260,21 +259,17 @@ int mmfs_bank_scatter(int dtype, int n_levels, void *const *grad_level_ptrs, con
     const int rc = make_levels(n_levels, grad_level_ptrs, level_hw, &L);
     if (rc) return rc;
     if (n_img == 0 || C == 0) return MMFS_OK;
-    if (n_slots > 0 && (!src_index || !grad_bank)) return MMFS_E_NULLPTR;
+    if (const int rt = check_tensors({{src_index, 1, n_slots > 0}, {grad_bank, 1, n_slots > 0}})) return rt;
     const int c_tiles = (int)((C + kTile - 1) / kTile);
     if ((int64_t)L.tiles * c_tiles > 0x7fffffffLL) return MMFS_E_DIMS;
     const dim3 grid((unsigned)(L.tiles * c_tiles), (unsigned)n_img);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMFS_F32)
-        hipLaunchKernelGGL((bank_scatter_kernel<float>), grid, dim3(kBankThreads), 0, st, L, src_index,
-                           (const float *)grad_bank, (int)C, (int)n_slots, c_tiles);
-    else if (dtype == MMFS_F16)
-        hipLaunchKernelGGL((bank_scatter_kernel<half_t>), grid, dim3(kBankThreads), 0, st, L, src_index,
-                           (const half_t *)grad_bank, (int)C, (int)n_slots, c_tiles);
-    else
-        hipLaunchKernelGGL((bank_scatter_kernel<bf16_t>), grid, dim3(kBankThreads), 0, st, L, src_index,
-                           (const bf16_t *)grad_bank, (int)C, (int)n_slots, c_tiles);
-    return (int)hipGetLastError();
+    return by_type(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipLaunchKernelGGL((bank_scatter_kernel<T>), grid, dim3(kBankThreads), 0, st, L, src_index, (const T *)grad_bank, (int)C,
+                           (int)n_slots, c_tiles);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // extern "C"

@@ -137,8 +137,7 @@ extern "C" int mmfs_bank_quantize_fp8(int dtype, const void *x, int64_t nbanks, 
     if (C % 16) return MMFS_E_UNSUPPORTED;                                   // (C = H*D, D a multiple of 16)
     const int64_t rows = nbanks * Bv;
     if (rows == 0 || C == 0) return MMFS_OK;
-    if (!x || !q || !scale) return MMFS_E_NULLPTR;
-    if ((((uintptr_t)x | (uintptr_t)q | (uintptr_t)scale) & 15) != 0) return MMFS_E_ALIGN;
+    if (const int rc = check_tensors({{x, 16}, {q, 16}, {scale, 16}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     return (int)by_type(dtype, [&](auto t) { return quantize<decltype(t)>(x, rows, R, C, q, scale, st); });
 }

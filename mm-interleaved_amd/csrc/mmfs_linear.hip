@@ -9,9 +9,8 @@
 // the tokens' activations sit in LDS (read as 16-byte vectors, conflict-free), products by the packed dot-product
 // instructions (two exact 16-bit products + fp32 accumulate per lane and instruction: no unpacking), one butterfly per
 // (row, token) at the end, bias added in fp32, ONE rounding to the storage type -- what the library's epilogue does.
-#include "../../include/mmfs_msda.h"
 #include "msda_env.h"
-#include "msda_device.h"
+#include "msda_host.h"
 #include "msda_dots.h"
 #include <cstdlib>
 
@@ -122,9 +121,10 @@ int mmfs_linear_small_add(int dtype, const void *x, const void *weight, const vo
     if (M < 0 || N < 0 || K < 0) return MMFS_E_DIMS;
     if (M == 0 || N == 0) return MMFS_OK;
     if (!mmfs_linear_small_supported(dtype, M, N, K)) return MMFS_E_UNSUPPORTED;
-    if (!x || !weight || !y) return MMFS_E_NULLPTR;
+    // (two phases: the leading dimensions are judged between the NULL pointers and the alignment)
+    if (const int rc = check_tensors({{x, 1}, {weight, 1}, {y, 1}})) return rc;
     if (ldx < K || ldy < N || (residual && ldr < N)) return MMFS_E_DIMS;
-    if (((uintptr_t)x | (uintptr_t)weight) % 16 || (ldx * 2) % 16) return MMFS_E_ALIGN;
+    if (check_tensors({{x, 16}, {weight, 16}}) || (ldx * 2) % 16) return MMFS_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int env_rows = mmfs::knob_int(mmfs::K_LIN_ROWS, 0);
     const int env_unroll = mmfs::knob_int(mmfs::K_LIN_UNROLL, 0);
@@ -135,19 +135,15 @@ int mmfs_linear_small_add(int dtype, const void *x, const void *weight, const vo
     const dim3 grid((unsigned)((N + per_wg - 1) / per_wg));
     const int mt = M <= 4 ? 4 : 8;
     const size_t lds = (size_t)mt * K * 2;
-#define MMFS_LIN(T, MT, R, U)                                                                                         \
-    hipLaunchKernelGGL((linear_small<T, MT, R, U>), grid, dim3(kLinThreads), lds, st, (const T *)x, (const T *)weight, \
-                       (const T *)bias, (const T *)residual, (T *)y, (int)M, (int)N, (int)K, ldx, ldy, ldr, early)
-#define MMFS_LIN_RU(T, MT)                                                                                            \
-    do {                                                                                                              \
-        if (rows == 1) { if (unroll == 8) MMFS_LIN(T, MT, 1, 8); else MMFS_LIN(T, MT, 1, 4); }                        \
-        else { if (unroll == 8) MMFS_LIN(T, MT, 2, 8); else MMFS_LIN(T, MT, 2, 4); }                                  \
-    } while (0)
-    if (dtype == MMFS_F16) { if (mt == 4) MMFS_LIN_RU(half_t, 4); else MMFS_LIN_RU(half_t, 8); }
-    else { if (mt == 4) MMFS_LIN_RU(bf16_t, 4); else MMFS_LIN_RU(bf16_t, 8); }
-#undef MMFS_LIN_RU
-#undef MMFS_LIN
-    return (int)hipGetLastError();
+    return by_half_type(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return by_int<4, 8>(mt, [&](auto m) { return by_int<1, 2>(rows, [&](auto r) { return by_int<8, 4>(unroll, [&](auto u) {
+            hipLaunchKernelGGL((linear_small<T, decltype(m)::value, decltype(r)::value, decltype(u)::value>), grid,
+                               dim3(kLinThreads), lds, st, (const T *)x, (const T *)weight, (const T *)bias, (const T *)residual,
+                               (T *)y, (int)M, (int)N, (int)K, ldx, ldy, ldr, early);
+            return (int)hipGetLastError();
+        }); }); });
+    });
 }
 
 int mmfs_linear_small(int dtype, const void *x, const void *weight, const void *bias, void *y,

@@ -321,12 +321,10 @@ int mmfs_llama_attn_rope_append(int dtype, const void *q, const void *k, const v
     if (rc) return rc;
     if (max_pos < 0 || max_pos > (1LL << 40) || B * Lq > (1LL << 32) || B * Lq * H > (1LL << 34)) return MMFS_E_DIMS;
     if (B * H == 0) return MMFS_OK;
-    if (!q || !k || !v || !position_ids || !length || !q_rot || !k_cache || !v_cache || !src_row) return MMFS_E_NULLPTR;
-    if (max_pos && (!cos_table || !sin_table)) return MMFS_E_NULLPTR;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_rot | (uintptr_t)k_cache | (uintptr_t)v_cache |
-         (uintptr_t)cos_table | (uintptr_t)sin_table) % 16 ||
-        (uintptr_t)position_ids % 8 || ((uintptr_t)length | (uintptr_t)src_row) % 4)
-        return MMFS_E_ALIGN;
+    const bool rope = max_pos != 0;
+    if (const int rt = check_tensors({{q, 16}, {k, 16}, {v, 16}, {position_ids, 8}, {length, 4}, {q_rot, 16}, {k_cache, 16},
+                                      {v_cache, 16}, {src_row, 4}, {cos_table, 16, rope}, {sin_table, 16, rope}}))
+        return rt;
     const int64_t total = B * Lq * H * 8;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
@@ -364,10 +362,9 @@ int mmfs_llama_attn_decode(int dtype, const void *q_rot, const void *k_cache, co
     if (rc) return rc;
     if (bias && ((bias_stride != 0 && bias_stride < bias_len) || bias_stride > kLlamaMaxCap)) return MMFS_E_DIMS;
     if (B * H == 0) return MMFS_OK;
-    if (!q_rot || !k_cache || !v_cache || !src_row || !length || !context || !workspace) return MMFS_E_NULLPTR;
-    if (((uintptr_t)q_rot | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)context | (uintptr_t)workspace) % 16 ||
-        ((uintptr_t)src_row | (uintptr_t)length) % 4 || !small_aligned((uintptr_t)bias, bias_f32))
-        return MMFS_E_ALIGN;
+    if ((rc = check_tensors({{q_rot, 16}, {k_cache, 16}, {v_cache, 16}, {src_row, 4}, {length, 4}, {context, 16}, {workspace, 16},
+                             maybe(bias, bias_f32 ? 4 : 2)})))
+        return rc;
     const int64_t splits = splits_of(kv_bound);
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;

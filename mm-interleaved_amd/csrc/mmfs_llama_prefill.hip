@@ -393,10 +393,9 @@ int mmfs_llama_attn_prefill(int dtype, const void *q_rot, const void *k_cache, c
     const int64_t tiles = (Lq + kRows - 1) / kRows;
     if (tiles * B * H > ((int64_t)1 << 31) - 1) return MMFS_E_DIMS;
     if (B * H == 0) return MMFS_OK;
-    if (!q_rot || !k_cache || !v_cache || !src_row || !length || !context) return MMFS_E_NULLPTR;
-    if (((uintptr_t)q_rot | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)context) % 16 ||
-        ((uintptr_t)src_row | (uintptr_t)length) % 4 || !small_aligned((uintptr_t)bias, bias_f32))
-        return MMFS_E_ALIGN;
+    if ((rc = check_tensors({{q_rot, 16}, {k_cache, 16}, {v_cache, 16}, {src_row, 4}, {length, 4}, {context, 16},
+                             maybe(bias, bias_f32 ? 4 : 2)})))
+        return rc;
     // a bias with a row per query whose rows all start 4 elements aligned is read 4 keys a lane
     const int bias_wide = bias && bias_query_stride && (uintptr_t)bias % (bias_f32 ? 16 : 8) == 0 && bias_query_stride % 4 == 0 &&
                           bias_batch_stride % 4 == 0;

@@ -661,7 +661,7 @@ int64_t mmfs_llama_attn_train_tiles(int level)
 int64_t mmfs_llama_attn_train_workspace_bytes(int64_t B, int64_t H, int64_t L)
 {
     using namespace mmfs;
-    if (B < 0 || H < 0 || L < 0 || L > kLlamaTrainMaxL || B > (1 << 20) || H > (1 << 20) || B * H > (1 << 24)) return MMFS_E_DIMS;
+    if (attn::batch_heads_check(MMFS_F16, B, H, L, 0, 0) || L > kLlamaTrainMaxL) return MMFS_E_DIMS;       // (no dtype to ask about)
     return B * H * L * (int64_t)sizeof(float);                             // delta
 }
 
@@ -673,10 +673,10 @@ int mmfs_llama_attn_train_rope(int dtype, const void *q, const void *k, const in
     bool empty;
     const int rc = train_check(dtype, B, H, D, L, max_pos, empty);
     if (rc || empty) return rc;
-    if (!q || !k || !position_ids || !q_rot || !k_rot || (max_pos && (!cos_table || !sin_table))) return MMFS_E_NULLPTR;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)q_rot | (uintptr_t)k_rot | (uintptr_t)cos_table | (uintptr_t)sin_table) % 16 ||
-        (uintptr_t)position_ids % 8)
-        return MMFS_E_ALIGN;
+    const bool rope = max_pos != 0;
+    if (const int rt = check_tensors({{q, 16}, {k, 16}, {position_ids, 8}, {q_rot, 16}, {k_rot, 16}, {cos_table, 16, rope},
+                                      {sin_table, 16, rope}}))
+        return rt;
     const int64_t total = B * L * H * 8;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
@@ -694,8 +694,7 @@ int mmfs_llama_attn_train_forward(int dtype, const void *q_rot, const void *k_ro
     bool empty;
     const int rc = train_check(dtype, B, H, D, L, 0, empty);
     if (rc || empty) return rc;
-    if (!q_rot || !k_rot || !v || !context || !lse) return MMFS_E_NULLPTR;
-    if (((uintptr_t)q_rot | (uintptr_t)k_rot | (uintptr_t)v | (uintptr_t)context) % 16 || (uintptr_t)lse % 4) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{q_rot, 16}, {k_rot, 16}, {v, 16}, {context, 16}, {lse, 4}})) return rt;
     const int64_t tiles = (L + kRows - 1) / kRows;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
@@ -714,13 +713,11 @@ int mmfs_llama_attn_train_backward(int dtype, const void *q_rot, const void *k_r
     bool empty;
     const int rc = train_check(dtype, B, H, D, L, max_pos, empty);
     if (rc || empty) return rc;
-    if (!q_rot || !k_rot || !v || !context || !grad_context || !lse || !position_ids || !grad_q || !grad_k || !grad_v ||
-        !workspace || (max_pos && (!cos_table || !sin_table)))
-        return MMFS_E_NULLPTR;
-    if (((uintptr_t)q_rot | (uintptr_t)k_rot | (uintptr_t)v | (uintptr_t)context | (uintptr_t)grad_context | (uintptr_t)grad_q |
-         (uintptr_t)grad_k | (uintptr_t)grad_v | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)workspace) % 16 ||
-        (uintptr_t)position_ids % 8 || (uintptr_t)lse % 4)
-        return MMFS_E_ALIGN;
+    const bool rope = max_pos != 0;
+    if (const int rt = check_tensors({{q_rot, 16}, {k_rot, 16}, {v, 16}, {context, 16}, {grad_context, 16}, {lse, 4},
+                                      {position_ids, 8}, {grad_q, 16}, {grad_k, 16}, {grad_v, 16}, {workspace, 16},
+                                      {cos_table, 16, rope}, {sin_table, 16, rope}}))
+        return rt;
     const int64_t qtiles = (L + kRows - 1) / kRows, ktiles = (L + kKeys - 1) / kKeys;
     return by_half_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;

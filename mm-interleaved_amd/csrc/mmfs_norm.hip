@@ -181,15 +181,11 @@ int norm_nv(int dtype, int64_t C)
     return nv;
 }
 
-// KERNEL<T, nv> (nv: norm_nv of the row length); inside by_type's lambda, T its storage type
-#define MMFS_NORM_DISPATCH(KERNEL, T, ...)                                                                        \
-    switch (nv) {                                                                                                 \
-        case 1: hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;    \
-        case 2: hipLaunchKernelGGL((KERNEL<T, 2>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;    \
-        case 4: hipLaunchKernelGGL((KERNEL<T, 4>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;    \
-        case 8: hipLaunchKernelGGL((KERNEL<T, 8>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;    \
-        default: hipLaunchKernelGGL((KERNEL<T, 16>), dim3(grid), dim3(kNormThreads), 0, st, __VA_ARGS__); break;  \
-    }
+// f(T(), nv as a constant) for the storage type and norm_nv of a row: the kernels are KERNEL<T, nv>
+template <typename F> int by_type_and_vectors(int dtype, int64_t C, F &&f)
+{
+    return by_type(dtype, [&](auto t) { return by_int<1, 2, 4, 8, 16>(norm_nv(dtype, C), [&](auto nv) { return f(t, nv); }); });
+}
 
 int norm_grid(int64_t rows)
 {
@@ -217,15 +213,13 @@ int mmfs_rmsnorm_forward(int dtype, const void *x, const void *weight, void *y, 
     if (rows < 0 || C < 0) return MMFS_E_DIMS;
     if (rows == 0 || C == 0) return MMFS_OK;
     if (!mmfs_rmsnorm_supported(dtype, C)) return MMFS_E_UNSUPPORTED;
-    if (!x || !weight || !y) return MMFS_E_NULLPTR;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) % 16) return MMFS_E_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = mmfs::norm_grid(rows);
     using namespace mmfs;
-    const int nv = norm_nv(dtype, C);
-    return by_type(dtype, [&](auto t) {
+    if (const int rc = check_tensors({{x, 16}, {weight, 16}, {y, 16}})) return rc;      // (rstd: not looked at)
+    const int grid = norm_grid(rows);
+    return by_type_and_vectors(dtype, C, [&](auto t, auto nv) {
         using T = decltype(t);
-        MMFS_NORM_DISPATCH(rmsnorm_fwd, T, (const T *)x, (const T *)weight, (T *)y, rstd, rows, (int)C, eps);
+        hipLaunchKernelGGL((rmsnorm_fwd<T, decltype(nv)::value>), dim3(grid), dim3(kNormThreads), 0, (hipStream_t)stream,
+                           (const T *)x, (const T *)weight, (T *)y, rstd, rows, (int)C, eps);
         return (int)hipGetLastError();
     });
 }
@@ -237,14 +231,12 @@ static int rmsnorm_backward_impl(int dtype, const void *grad_y, const void *x, c
     if (rows < 0 || C < 0) return MMFS_E_DIMS;
     if (rows == 0 || C == 0) return MMFS_OK;
     if (!mmfs_rmsnorm_supported(dtype, C)) return MMFS_E_UNSUPPORTED;
-    if (!grad_y || !x || !weight || !rstd || !grad_x || !gw) return MMFS_E_NULLPTR;
-    if (((uintptr_t)grad_y | (uintptr_t)x | (uintptr_t)weight | (uintptr_t)grad_x) % 16) return MMFS_E_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
     using namespace mmfs;
-    const int nv = norm_nv(dtype, C);
-    return by_type(dtype, [&](auto t) {
+    if (const int rc = check_tensors({{grad_y, 16}, {x, 16}, {weight, 16}, {rstd, 1}, {grad_x, 16}, {gw, 1}})) return rc;
+    return by_type_and_vectors(dtype, C, [&](auto t, auto nv) {
         using T = decltype(t);
-        MMFS_NORM_DISPATCH(rmsnorm_bwd, T, (const T *)grad_y, (const T *)x, (const T *)weight, rstd, (T *)grad_x, gw, rows, (int)C, partials);
+        hipLaunchKernelGGL((rmsnorm_bwd<T, decltype(nv)::value>), dim3(grid), dim3(kNormThreads), 0, (hipStream_t)stream,
+                           (const T *)grad_y, (const T *)x, (const T *)weight, rstd, (T *)grad_x, gw, rows, (int)C, partials);
         return (int)hipGetLastError();
     });
 }

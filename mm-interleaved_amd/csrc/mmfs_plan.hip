@@ -578,15 +578,12 @@ int check_dims(int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P, int64_t n
 }  // namespace
 }  // namespace mmfs
 
-// dispatch over the points per row P (4, 8, 16) and the lane-group width G (pow2 >= n*L)
-template <typename T, int P, typename F>
-static int for_group(int nL, F &&f)
+// dispatch over the lane-group width G (the power of two >= n*L, 4 .. 64); the points per row P: by_int<4, 8, 16>
+template <typename F> static int for_group(int nL, F &&f)
 {
-    if (nL <= 4) return f(std::integral_constant<int, 4>());
-    if (nL <= 8) return f(std::integral_constant<int, 8>());
-    if (nL <= 16) return f(std::integral_constant<int, 16>());
-    if (nL <= 32) return f(std::integral_constant<int, 32>());
-    return f(std::integral_constant<int, 64>());
+    int G = 4;
+    while (G < nL) G *= 2;
+    return mmfs::by_int<4, 8, 16, 32, 64>(G, f);
 }
 
 extern "C" {
@@ -616,9 +613,10 @@ int mmfs_plan_forward_heads(int dtype, const void *off_q, const void *att_q, int
     if (rc) return rc;
     const int64_t items = N * Lq * H;
     if (items == 0) return MMFS_OK;
-    if (!off_q || !att_q || !off_tab || !att_tab || !relpos || !ref || !shapes || !ratios || !loc || !attn || !sink)
-        return MMFS_E_NULLPTR;
-    int rr;
+    // (the rows of the four matrices: heads_rows; nothing else is refused for its alignment)
+    int rr = check_tensors({{off_q, 1}, {att_q, 1}, {off_tab, 1}, {att_tab, 1}, {relpos, 1}, {ref, 1}, {shapes, 1}, {ratios, 1},
+                            {loc, 1}, {attn, 1}, {sink, 1}});
+    if (rr) return rr;
     if ((rr = heads_rows(ld_off, H * 2 * P, off_q, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, att_q, P, es)) ||
         (rr = heads_rows(ld_toff, H * 2 * P, off_tab, 2 * P, es)) || (rr = heads_rows(ld_tatt, H * L * P, att_tab, P, es)))
         return rr;
@@ -627,7 +625,7 @@ int mmfs_plan_forward_heads(int dtype, const void *off_q, const void *att_q, int
     auto go = [&](auto tag_t, auto tag_p) {
         typedef decltype(tag_t) T;
         constexpr int PP = decltype(tag_p)::value;
-        return for_group<T, PP>(d.n * d.L, [&](auto tag_g) {
+        return for_group(d.n * d.L, [&](auto tag_g) {
             constexpr int G = decltype(tag_g)::value;
             const unsigned blocks = (unsigned)((items + kThreads / G - 1) / (kThreads / G));
             hipLaunchKernelGGL((plan_forward_kernel<T, PP, G>), dim3(blocks), dim3(kThreads), 0, st,
@@ -636,12 +634,7 @@ int mmfs_plan_forward_heads(int dtype, const void *off_q, const void *att_q, int
             return (int)hipGetLastError();
         });
     };
-    auto by_p = [&](auto tag_t) {
-        if (P == 4) return go(tag_t, std::integral_constant<int, 4>());
-        if (P == 8) return go(tag_t, std::integral_constant<int, 8>());
-        return go(tag_t, std::integral_constant<int, 16>());
-    };
-    return by_type(dtype, by_p);
+    return by_type(dtype, [&](auto tag_t) { return by_int<4, 8, 16>(P, [&](auto tag_p) { return go(tag_t, tag_p); }); });
 }
 
 int mmfs_plan_backward(int dtype, const void *grad_loc, const void *grad_attn, const float *grad_sink,
@@ -670,11 +663,11 @@ int mmfs_plan_backward_heads(int dtype, const void *grad_loc, const void *grad_a
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &d);
     if (rc) return rc;
     if (N * Lq * H == 0) return MMFS_OK;
-    if (!grad_loc || !grad_attn || !attn || !sink || !relpos || !shapes || !ratios || !d_off_q || !d_att_q ||
-        !d_off_tab || !d_att_tab)
-        return MMFS_E_NULLPTR;
+    // (grad_sink may be NULL; the rows of the four gradients: heads_rows)
+    int rr = check_tensors({{grad_loc, 1}, {grad_attn, 1}, {attn, 1}, {sink, 1}, {relpos, 1}, {shapes, 1}, {ratios, 1},
+                            {d_off_q, 1}, {d_att_q, 1}, {d_off_tab, 1}, {d_att_tab, 1}});
+    if (rr) return rr;
     const int qes = q_grads_in_storage_type ? es : 4;
-    int rr;
     if ((rr = heads_rows(ld_off, H * 2 * P, d_off_q, 2 * P, qes)) || (rr = heads_rows(ld_att, H * L * P, d_att_q, P, qes)) ||
         (rr = heads_rows(ld_toff, H * 2 * P, d_off_tab, 1, 4)) || (rr = heads_rows(ld_tatt, H * L * P, d_att_tab, 1, 4)))
         return rr;
@@ -684,7 +677,7 @@ int mmfs_plan_backward_heads(int dtype, const void *grad_loc, const void *grad_a
     auto go = [&](auto tag_t, auto tag_p) {
         typedef decltype(tag_t) T;
         constexpr int PP = decltype(tag_p)::value;
-        return for_group<T, PP>(d.n * d.L, [&](auto tag_g) {
+        return for_group(d.n * d.L, [&](auto tag_g) {
             constexpr int G = decltype(tag_g)::value;
             const unsigned blocks = (unsigned)((units + kThreads / G - 1) / (kThreads / G));
             if (q_grads_in_storage_type && !std::is_same<T, float>::value)
@@ -698,12 +691,7 @@ int mmfs_plan_backward_heads(int dtype, const void *grad_loc, const void *grad_a
             return (int)hipGetLastError();
         });
     };
-    auto by_p = [&](auto tag_t) {
-        if (P == 4) return go(tag_t, std::integral_constant<int, 4>());
-        if (P == 8) return go(tag_t, std::integral_constant<int, 8>());
-        return go(tag_t, std::integral_constant<int, 16>());
-    };
-    return by_type(dtype, by_p);
+    return by_type(dtype, [&](auto tag_t) { return by_int<4, 8, 16>(P, [&](auto tag_p) { return go(tag_t, tag_p); }); });
 }
 
 int mmfs_sample_forward(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
@@ -789,8 +777,8 @@ static int sample_forward_any(int dtype, bool fp8, const void *value, const floa
     PlanDims pd;
     const int rc = check_dims(N, Lq, H, L, P, n, M, Lr, Nr, &pd);
     if (rc) return rc;
-    if (Nv <= 0 || N % Nv != 0) return MMFS_E_DIMS;
-    if (layout != MMFS_BANK_TILE && layout != MMFS_BANK_INTERLEAVE) return MMFS_E_UNSUPPORTED;
+    Dims d;
+    if (const int rb = set_bank(&d, N, Nv, layout)) return rb;              // (Nv = N: the unshared call)
     if (S < 0 || D <= 0 || S > 0x7ffffffdLL || H * D > 0x7fffffffLL) return MMFS_E_DIMS;
     if (N * Lq * H == 0) return MMFS_OK;
     if (P == 16 || S == 0) return MMFS_E_UNSUPPORTED;                       // (P = 16: the two-kernel path)
@@ -799,23 +787,17 @@ static int sample_forward_any(int dtype, bool fp8, const void *value, const floa
     const int lpi = (int)(D / vec);
     if (lpi < 1 || lpi > (fp8 ? 16 : 64) || (lpi & (lpi - 1))) return MMFS_E_UNSUPPORTED;
     if (S * H * D * (int64_t)bes > kMaxSlabBytes) return MMFS_E_UNSUPPORTED;       // buffer-descriptor rows only
-    if (!value || !shapes || !start || !off_q || !att_q || !off_tab || !att_tab || !relpos || !ref || !ratios || !out ||
-        (fp8 && !scale))
-        return MMFS_E_NULLPTR;
-    if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)token | (uintptr_t)scale) % 16) return MMFS_E_ALIGN;
+    int rr = check_tensors({{value, 16}, {out, 16}, maybe(token, 16), {scale, 16, fp8}, {shapes, 1}, {start, 1}, {off_q, 1},
+                            {att_q, 1}, {off_tab, 1}, {att_tab, 1}, {relpos, 1}, {ref, 1}, {ratios, 1}});
+    if (rr) return rr;
     // token rows of off_q / att_q: packed, or ld elements apart (columns of one wider matrix); vector loads of P
-    // (2 P) elements need the rows aligned like the packed ones
-    if (ld_off == 0) ld_off = H * 2 * P;
-    if (ld_att == 0) ld_att = H * L * P;
-    if (ld_off < H * 2 * P || ld_att < H * L * P || ld_off > 0x7fffffffLL || ld_att > 0x7fffffffLL) return MMFS_E_DIMS;
-    if ((ld_off * es) % (2 * P * es) || (ld_att * es) % (P * es) || (uintptr_t)off_q % (2 * P * es) || (uintptr_t)att_q % (P * es))
-        return MMFS_E_ALIGN;
+    // (2 P) elements need the rows aligned like the packed ones -- to the whole row of a point, not heads_rows' 16 bytes
+    if ((rr = rows_range(ld_off, H * 2 * P)) || (rr = rows_range(ld_att, H * L * P)) ||
+        (rr = rows_aligned(ld_off, es, off_q, 2 * P * es)) || (rr = rows_aligned(ld_att, es, att_q, P * es)))
+        return rr;
     pd.ld_off = (int)ld_off; pd.ld_att = (int)ld_att;
-    Dims d;
     d.B = (int)N; d.S = (int)S; d.H = (int)H; d.D = (int)D; d.L = (int)(n * L); d.Nq = (int)Lq; d.P = (int)P;
     d.K = d.L * d.P; d.lazy_attn = 0; d.blocks4 = 0;
-    d.Bv = (int)Nv;                                                         // (Nv = N: the unshared call)
-    d.vdiv = layout == MMFS_BANK_INTERLEAVE ? (int)(N / Nv) : 1;
     int G = 4;
     while (G < d.L) G *= 2;                                                 // the plan kernel's lane-group width
     hipStream_t st = (hipStream_t)stream;
@@ -850,35 +832,15 @@ static int sample_forward_any(int dtype, bool fp8, const void *value, const floa
     };
     const bool decode = sample_groups(Lq, d.K, d.L, lpi) > 1;
     auto by_p = [&](auto tag_t, auto tag_b, auto tag_lpi) {
-        if (decode) {
-            if (P == 4) return go_decode(tag_t, tag_b, tag_lpi, std::integral_constant<int, 4>());
-            return go_decode(tag_t, tag_b, tag_lpi, std::integral_constant<int, 8>());
-        }
-        if (P == 4) return go(tag_t, tag_b, tag_lpi, std::integral_constant<int, 4>());
-        return go(tag_t, tag_b, tag_lpi, std::integral_constant<int, 8>());
+        return by_int<4, 8>(P, [&](auto tag_p) {
+            return decode ? go_decode(tag_t, tag_b, tag_lpi, tag_p) : go(tag_t, tag_b, tag_lpi, tag_p);
+        });
     };
     auto by_lpi = [&](auto tag_t) {
         typedef decltype(tag_t) T;
-        if (fp8) {                                                         // (16 channels per lane: D = 16 .. 256)
-            const fp8e4m3_t b{};
-            switch (lpi) {
-                case 1: return by_p(tag_t, b, std::integral_constant<int, 1>());
-                case 2: return by_p(tag_t, b, std::integral_constant<int, 2>());
-                case 4: return by_p(tag_t, b, std::integral_constant<int, 4>());
-                case 8: return by_p(tag_t, b, std::integral_constant<int, 8>());
-                default: return by_p(tag_t, b, std::integral_constant<int, 16>());
-            }
-        }
-        const T b{};
-        switch (lpi) {
-            case 1: return by_p(tag_t, b, std::integral_constant<int, 1>());
-            case 2: return by_p(tag_t, b, std::integral_constant<int, 2>());
-            case 4: return by_p(tag_t, b, std::integral_constant<int, 4>());
-            case 8: return by_p(tag_t, b, std::integral_constant<int, 8>());
-            case 16: return by_p(tag_t, b, std::integral_constant<int, 16>());
-            case 32: return by_p(tag_t, b, std::integral_constant<int, 32>());
-            default: return by_p(tag_t, b, std::integral_constant<int, 64>());
-        }
+        if (fp8)                                                           // (16 channels per lane: D = 16 .. 256)
+            return by_int<1, 2, 4, 8, 16>(lpi, [&](auto tag_lpi) { return by_p(tag_t, fp8e4m3_t{}, tag_lpi); });
+        return by_int<1, 2, 4, 8, 16, 32, 64>(lpi, [&](auto tag_lpi) { return by_p(tag_t, T{}, tag_lpi); });
     };
     return by_type(dtype, by_lpi);
 }

@@ -407,16 +407,12 @@ int mmfs_pyramid_head_forward(int dtype, const void *c, const void *x1, const vo
     Plan p;
     const int rc = make_plan(dtype, B, H, W, C, levels, c1_layout, &p);
     if (rc || p.empty) return rc;
-    const void *xs[4] = {x1, x2, x3, x4};
-    for (int l = 0; l < 4; ++l)
-        if (((levels >> l) & 1) && !xs[l]) return MMFS_E_NULLPTR;
-    if (!out || ((levels & 1) && (!up || !c1)) || ((levels & 14) && !c)) return MMFS_E_NULLPTR;
-    const float *ps[4] = {pos1, pos2, pos3, pos4};
-    uintptr_t bits = (uintptr_t)out | ((levels & 14) ? (uintptr_t)c : 0) | ((levels & 1) ? (uintptr_t)up | (uintptr_t)c1 : 0);
-    for (int l = 0; l < 4; ++l)
-        if ((levels >> l) & 1) bits |= (uintptr_t)xs[l] | (uintptr_t)ps[l];
-    if (bits % 16)
-        return MMFS_E_ALIGN;
+    // a level's pointers are looked at only if the mask has the level; its position table may be NULL
+    auto of = [&](int mask, const void *p, bool needed) { return Tensor{(levels & mask) ? p : nullptr, 16, (levels & mask) && needed}; };
+    if (const int rt = check_tensors({{out, 16}, of(14, c, true), of(1, up, true), of(1, c1, true), of(1, x1, true), of(2, x2, true),
+                                      of(4, x3, true), of(8, x4, true), of(1, pos1, false), of(2, pos2, false), of(4, pos3, false),
+                                      of(8, pos4, false)}))
+        return rt;
     return by_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         if (p.fwd_total) {
@@ -441,19 +437,16 @@ int mmfs_pyramid_head_backward(int dtype, const void *grad_out, void *grad_up, v
     Plan p;
     const int rc = make_plan(dtype, B, H, W, C, levels, c1_layout, &p);
     if (rc || p.empty) return rc;
-    if (!grad_out) return MMFS_E_NULLPTR;
     const bool rows1 = c1_layout == MMFS_PYRAMID_C1_NHWC;
     // a NULL output is a gradient nobody asked for: its segment leaves the row walk (pointers of levels outside the mask
     // are not looked at)
     void *gx[4] = {grad_x1, grad_x2, grad_x3, grad_x4};
-    uintptr_t bits = (uintptr_t)grad_out;
-    for (int l = 0; l < 4; ++l) {
+    for (int l = 0; l < 4; ++l)
         if (!((levels >> l) & 1)) gx[l] = nullptr;
-        bits |= (uintptr_t)gx[l];
-    }
     if (!(levels & 1)) grad_up = grad_c1 = nullptr;
-    bits |= (uintptr_t)grad_up | (uintptr_t)grad_c1;
-    if (bits % 16) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{grad_out, 16}, maybe(gx[0], 16), maybe(gx[1], 16), maybe(gx[2], 16), maybe(gx[3], 16),
+                                      maybe(grad_up, 16), maybe(grad_c1, 16)}))
+        return rt;
     void *rows_c1 = rows1 ? grad_c1 : nullptr;
     const bool seg_on[5] = {grad_up || rows_c1, gx[0] != nullptr, gx[1] != nullptr, gx[2] != nullptr, gx[3] != nullptr};
     lay_out_backward(&p, B, seg_on);

@@ -15,9 +15,8 @@
 //     rounds again -- the roundings of the framework's two kernels;
 //   * ``tokens_add``: the way back, y[b, c, p] = round(tok[b, p, c] + res[b, c, p]) through the same tile.
 // Bytes-bound: each reads its input once and writes its output once.
-#include "../../include/mmfs_msda.h"
 #include "msda_env.h"
-#include "msda_device.h"
+#include "msda_host.h"
 #include <cstdlib>
 
 namespace mmfs {
@@ -230,22 +229,23 @@ int mmfs_query_prep(int dtype, const void *x, const void *gamma, const void *bet
     if (B < 0 || C < 0 || HW < 0) return MMFS_E_DIMS;
     if (B == 0 || C == 0 || HW == 0) return MMFS_OK;
     if (!query_ok(dtype, C, HW) || B > 65535) return MMFS_E_UNSUPPORTED;
-    if (!x || !gamma || !beta || !q || ((mean == nullptr) != (rstd == nullptr))) return MMFS_E_NULLPTR;
-    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pos | (uintptr_t)q) % 16) return MMFS_E_ALIGN;
+    // (mean and rstd: both or neither)
+    if (const int rc = check_tensors({{x, 16}, {gamma, 16}, {beta, 16}, maybe(pos, 16), {q, 16}, {mean, 1, rstd != nullptr},
+                                      {rstd, 1, mean != nullptr}}))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const int sh = query_tile_shift(C, HW), tp = 8 << sh;
     const dim3 grid((unsigned)((HW + tp - 1) / tp), (unsigned)B);
     const size_t lds = (size_t)tp * ((C + 63) / 64 * 64 + kQueryPad) * 2;
     const int nv = (int)((C / 8 + 63) / 64);
-#define MMFS_QP(T, NV)                                                                                              \
-    hipLaunchKernelGGL((query_prep<T, NV>), grid, dim3(kQueryThreads), lds, st, (const T *)x, (const T *)gamma,     \
-                       (const T *)beta, (const T *)pos, (T *)q, mean, rstd, (int)C, (int)HW, sh, eps)
-#define MMFS_QP_NV(T)                                                                                               \
-    do { if (nv <= 1) MMFS_QP(T, 1); else if (nv == 2) MMFS_QP(T, 2); else MMFS_QP(T, 4); } while (0)
-    if (dtype == MMFS_F16) MMFS_QP_NV(half_t); else MMFS_QP_NV(bf16_t);
-#undef MMFS_QP_NV
-#undef MMFS_QP
-    return (int)hipGetLastError();
+    return by_half_type(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        return by_int<1, 2, 4>(nv, [&](auto tag_nv) {                       // (nv >= 1; 3 takes the kernel of 4)
+            hipLaunchKernelGGL((query_prep<T, decltype(tag_nv)::value>), grid, dim3(kQueryThreads), lds, st, (const T *)x,
+                               (const T *)gamma, (const T *)beta, (const T *)pos, (T *)q, mean, rstd, (int)C, (int)HW, sh, eps);
+            return (int)hipGetLastError();
+        });
+    });
 }
 
 int mmfs_tokens_add(int dtype, const void *tok, const void *res, void *y, int64_t B, int64_t C, int64_t HW, void *stream)
@@ -255,17 +255,14 @@ int mmfs_tokens_add(int dtype, const void *tok, const void *res, void *y, int64_
     if (B < 0 || C < 0 || HW < 0) return MMFS_E_DIMS;
     if (B == 0 || C == 0 || HW == 0) return MMFS_OK;
     if (!query_ok(dtype, C, HW) || B > 65535) return MMFS_E_UNSUPPORTED;
-    if (!tok || !res || !y) return MMFS_E_NULLPTR;
-    if (((uintptr_t)tok | (uintptr_t)res | (uintptr_t)y) % 16) return MMFS_E_ALIGN;
+    if (const int rc = check_tensors({{tok, 16}, {res, 16}, {y, 16}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((HW + kAddPx - 1) / kAddPx), (unsigned)((C + kAddCh - 1) / kAddCh), (unsigned)B);
-    if (dtype == MMFS_F16)
-        hipLaunchKernelGGL((tokens_add<half_t>), grid, dim3(kQueryThreads), 0, st, (const half_t *)tok, (const half_t *)res,
-                           (half_t *)y, (int)C, (int)HW);
-    else
-        hipLaunchKernelGGL((tokens_add<bf16_t>), grid, dim3(kQueryThreads), 0, st, (const bf16_t *)tok, (const bf16_t *)res,
-                           (bf16_t *)y, (int)C, (int)HW);
-    return (int)hipGetLastError();
+    return by_half_type(dtype, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipLaunchKernelGGL((tokens_add<T>), grid, dim3(kQueryThreads), 0, st, (const T *)tok, (const T *)res, (T *)y, (int)C, (int)HW);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // extern "C"

@@ -48,7 +48,6 @@
 // the same call does not read again leave with the non-temporal hint.
 #include "msda_host.h"
 #include <hip/hip_runtime.h>
-#include <initializer_list>
 
 namespace mmfs {
 
@@ -327,13 +326,6 @@ seq_context_bwd_pad_sum(const float *__restrict__ scratch, T *__restrict__ grad_
 
 bool supported(int es, int64_t C) { return es && C > 0 && (C * es) % 16 == 0; }
 
-bool aligned16(std::initializer_list<const void *> ps)
-{
-    uintptr_t bits = 0;
-    for (const void *p : ps) bits |= (uintptr_t)p;
-    return bits % 16 == 0;
-}
-
 unsigned blocks_of(int64_t lanes) { return (unsigned)((lanes + kThreads - 1) / kThreads); }
 bool grid_fits(int64_t lanes) { return (lanes + kThreads - 1) / kThreads <= 0x7fffffffLL; }
 
@@ -374,11 +366,9 @@ int mmfs_sequence_index(const int64_t *text_ids, int64_t B, int64_t L, int64_t i
     if (B < 0 || L < 0 || n_vis < 0 || n_images < 0) return MMFS_E_DIMS;
     if (B > kMaxTokens || L > kMaxTokens || B * L > kMaxTokens || n_vis > kMaxTokens || n_images > kMaxTokens) return MMFS_E_DIMS;
     const int64_t N = B * L;
-    if (!row_first || !counts || (N && (!text_ids || !img_rank)) || (n_vis && !img_pos) || (n_images && (!soi_row || !soi_col)))
-        return MMFS_E_NULLPTR;
-    if ((uintptr_t)text_ids % 8 || ((uintptr_t)img_rank | (uintptr_t)img_pos | (uintptr_t)soi_row | (uintptr_t)soi_col |
-                                    (uintptr_t)row_first | (uintptr_t)counts) % 4)
-        return MMFS_E_ALIGN;
+    if (const int rc = check_tensors({{row_first, 4}, {counts, 4}, {text_ids, 8, N != 0}, {img_rank, 4, N != 0},
+                                      {img_pos, 4, n_vis != 0}, {soi_row, 4, n_images != 0}, {soi_col, 4, n_images != 0}}))
+        return rc;
     hipLaunchKernelGGL(seq_index, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, text_ids, (int)N, (int)B, (int)L,
                        image_token_id, soi_token_id, (int)n_vis, (int)n_images, img_rank, img_pos, soi_row, soi_col, row_first,
                        counts);
@@ -392,8 +382,8 @@ int mmfs_sequence_embed_forward(int dtype, int text_dtype, const void *text, con
     using namespace mmfs;
     const int rc = check_embed(dtype, text_dtype, rows, C, n_vis);
     if (rc || rows == 0) return rc;
-    if (!text || !soi_token || !text_ids || !img_rank || !out || (n_vis && !vis)) return MMFS_E_NULLPTR;
-    if (!aligned16({text, vis, soi_token, out}) || (uintptr_t)text_ids % 8 || (uintptr_t)img_rank % 4) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{text, 16}, {vis, 16, n_vis != 0}, {soi_token, 16}, {out, 16}, {text_ids, 8}, {img_rank, 4}}))
+        return rt;
     const int es = elem_size(dtype), CV = (int)(C * es / 16);
     const int64_t total = rows * CV;
     if (!grid_fits(total)) return MMFS_E_DIMS;
@@ -423,11 +413,11 @@ int mmfs_sequence_embed_backward(int dtype, int text_dtype, const void *grad, co
     if (!n_vis) grad_vis = nullptr;
     if (!rows) grad_text = nullptr;
     if (!grad_text && !grad_vis && !grad_soi) return MMFS_OK;
-    if ((rows && (!grad || !img_rank)) || (grad_vis && !img_pos) || (grad_soi && (!counts || (n_images && (!soi_row || !soi_col)))))
-        return MMFS_E_NULLPTR;
-    if (!aligned16({grad, grad_text, grad_vis, grad_soi}) ||
-        ((uintptr_t)img_rank | (uintptr_t)img_pos | (uintptr_t)soi_row | (uintptr_t)soi_col | (uintptr_t)counts) % 4)
-        return MMFS_E_ALIGN;
+    const bool soi = grad_soi != nullptr;
+    if (const int rt = check_tensors({{grad, 16, rows != 0}, {img_rank, 4, rows != 0}, {img_pos, 4, grad_vis != nullptr}, {counts, 4, soi},
+                                      {soi_row, 4, soi && n_images}, {soi_col, 4, soi && n_images}, maybe(grad_text, 16),
+                                      maybe(grad_vis, 16), maybe(grad_soi, 16)}))
+        return rt;
     const int es = elem_size(dtype), CV = (int)(C * es / 16);
     const int64_t total = (rows + n_vis + 1) * CV;
     if (!grid_fits(total)) return MMFS_E_DIMS;
@@ -453,10 +443,10 @@ int mmfs_sequence_context_forward(int dtype, const void *src, const void *pad_ro
     using namespace mmfs;
     const int rc = check_context(dtype, B, L, C, n_images, max_len, seq_len);
     if (rc || n_images == 0) return rc;
-    if (!soi_row || (!soi_col && !start_idx) || !mask || !out || (B * L && !src)) return MMFS_E_NULLPTR;
-    if (!aligned16({src, pad_row, pos, out}) || ((uintptr_t)start_idx | (uintptr_t)bos_idx | (uintptr_t)mask) % 8 ||
-        ((uintptr_t)soi_row | (uintptr_t)soi_col) % 4)
-        return MMFS_E_ALIGN;
+    // (the rows' first columns: soi_col, or start_idx in its place)
+    if (const int rt = check_tensors({{soi_row, 4}, {soi_col, 4, !start_idx}, maybe(start_idx, 8), maybe(bos_idx, 8), {mask, 8},
+                                      {out, 16}, {src, 16, B * L != 0}, maybe(pad_row, 16), maybe(pos, 16)}))
+        return rt;
     const int es = elem_size(dtype), CV = (int)(C * es / 16);
     const int64_t total = n_images * max_len * CV;
     if (!grid_fits(total)) return MMFS_E_DIMS;
@@ -489,12 +479,11 @@ int mmfs_sequence_context_backward(int dtype, const void *grad_out, const int32_
     if (rc) return rc;
     if (B * L == 0) grad_src = nullptr;
     if (!grad_src && !grad_pad) return MMFS_OK;
-    if ((n_images && (!grad_out || !soi_row || (!soi_col && !start_idx))) || (grad_src && !row_first) ||
-        (grad_pad && n_images && !workspace))
-        return MMFS_E_NULLPTR;
-    if (!aligned16({grad_out, grad_src, grad_pad, workspace}) || ((uintptr_t)start_idx | (uintptr_t)bos_idx) % 8 ||
-        ((uintptr_t)soi_row | (uintptr_t)soi_col | (uintptr_t)row_first) % 4)
-        return MMFS_E_ALIGN;
+    const bool im = n_images != 0;
+    if (const int rt = check_tensors({{grad_out, 16, im}, {soi_row, 4, im}, {soi_col, 4, im && !start_idx}, maybe(start_idx, 8),
+                                      maybe(bos_idx, 8), {row_first, 4, grad_src != nullptr}, {workspace, 16, grad_pad && im},
+                                      maybe(grad_src, 16), maybe(grad_pad, 16)}))
+        return rt;
     const int es = elem_size(dtype), CV = (int)(C * es / 16);
     const int64_t src_total = B * L * CV, pad_total = n_images * CV;
     if (!grid_fits(src_total) || !grid_fits(pad_total)) return MMFS_E_DIMS;

@@ -286,10 +286,10 @@ int mmfs_text_loss_forward(int dtype, const void *logits, const int64_t *labels,
     const int rc = check(dtype, B, L, V, first, n, reduction);
     if (rc) return rc;
     const int64_t rows = B * n;
-    if (!counts || (reduction != kNone && !out) || (rows && (!logits || !labels || !loss || !lse))) return MMFS_E_NULLPTR;
-    if ((uintptr_t)logits % 16 || (uintptr_t)labels % 8 ||
-        ((uintptr_t)loss | (uintptr_t)lse | (uintptr_t)out | (uintptr_t)counts) % 4)
-        return MMFS_E_ALIGN;
+    const bool any = rows != 0;
+    if (const int rt = check_tensors({{counts, 4}, {out, 4, reduction != kNone}, {logits, 16, any}, {labels, 8, any}, {loss, 4, any},
+                                      {lse, 4, any}}))
+        return rt;
     if (rows) {
         const int e = by_type(dtype, [&](auto tag) {
             typedef decltype(tag) T;
@@ -312,10 +312,10 @@ int mmfs_text_loss_backward(int dtype, const void *logits, const int64_t *labels
     const int rc = check(dtype, B, L, V, first, n, reduction);
     if (rc) return rc;
     if (B * L == 0) return MMFS_OK;
-    if (!grad || (B * n && (!logits || !labels || !lse || !upstream || (reduction == kMean && !counts)))) return MMFS_E_NULLPTR;
-    if (((uintptr_t)logits | (uintptr_t)grad) % 16 || (uintptr_t)labels % 8 ||
-        ((uintptr_t)lse | (uintptr_t)upstream | (uintptr_t)counts) % 4)
-        return MMFS_E_ALIGN;
+    const bool any = B * n != 0;
+    if (const int rt = check_tensors({{grad, 16}, {logits, 16, any}, {labels, 8, any}, {lse, 4, any}, {upstream, 4, any},
+                                      {counts, 4, any && reduction == kMean}}))
+        return rt;
     return by_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
         hipLaunchKernelGGL((text_loss_bwd<T>), dim3((unsigned)(B * L)), dim3(kThreads), 0, (hipStream_t)stream,

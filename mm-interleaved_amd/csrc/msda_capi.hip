@@ -7,9 +7,15 @@
 #include "msda_plan.h"
 #include <cstring>
 #include <cstdlib>
-#include <initializer_list>
 
 namespace {
+
+using mmfs::Tensor;
+using mmfs::check_tensors;
+using mmfs::check_workspace;
+using mmfs::misaligned;
+using mmfs::round256;
+using mmfs::set_bank;
 
 // What every entry point works out first: the element size (the op alone serves fp64), the dims narrowed to the
 // kernels' 32-bit index range, and the three element counts.
@@ -57,38 +63,6 @@ void decode_bwd_flags(mmfs::Dims *d, unsigned flags)
     d->lazy_attn = (flags & MMFS_BWD_LAZY_ZERO_ATTN) ? 1 : 0;
     d->taps_algo = (flags & MMFS_BWD_TAPS_LDS_LEVELS) ? 2 : (flags & MMFS_BWD_TAPS_ROW_GATHER) ? 1 : 0;
 }
-
-// A bank of Bv rows behind B query rows (MMFS_BANK_*): MMFS_E_DIMS / MMFS_E_UNSUPPORTED, or d->Bv and d->vdiv set.
-int set_bank(mmfs::Dims *d, int64_t B, int64_t Bv, int layout)
-{
-    if (Bv <= 0 || B % Bv != 0) return MMFS_E_DIMS;
-    if (layout != MMFS_BANK_TILE && layout != MMFS_BANK_INTERLEAVE) return MMFS_E_UNSUPPORTED;
-    if (B > 0) {
-        d->Bv = (int)Bv;
-        d->vdiv = layout == MMFS_BANK_INTERLEAVE ? (int)(B / Bv) : 1;
-    }
-    return MMFS_OK;
-}
-
-bool misaligned(const void *p, int esize) { return ((uintptr_t)p % (uintptr_t)esize) != 0; }
-
-// An entry point's pointer contract, as a list: MMFS_E_NULLPTR if any pointer is NULL, else MMFS_E_ALIGN if any is not
-// a multiple of its alignment (1: a level table, which no entry refuses for its alignment).
-struct Tensor { const void *p; int align; };
-int check_tensors(std::initializer_list<Tensor> ts)
-{
-    for (const Tensor &t : ts) if (!t.p) return MMFS_E_NULLPTR;
-    for (const Tensor &t : ts) if (misaligned(t.p, t.align)) return MMFS_E_ALIGN;
-    return MMFS_OK;
-}
-
-int check_workspace(const void *workspace, int64_t have, int64_t need)
-{
-    if (!workspace || have < need) return MMFS_E_NULLPTR;
-    return misaligned(workspace, 16) ? MMFS_E_ALIGN : MMFS_OK;
-}
-
-int64_t round256(int64_t x) { return (x + 255) / 256 * 256; }
 
 // the vector kernels move 16-byte channel vectors; rows are D*es apart, so the bases must be 16-byte aligned whenever
 // D*es is a multiple of 16

@@ -279,11 +279,7 @@ int check_dims(int dtype, int64_t N, int64_t Lq, int64_t H, int64_t L, int64_t P
 
 template <typename F> int by_type_and_points(int dtype, int64_t P, F &&f)
 {
-    return by_type(dtype, [&](auto tag_t) {
-        if (P == 2) return f(tag_t, std::integral_constant<int, 2>());
-        if (P == 4) return f(tag_t, std::integral_constant<int, 4>());
-        return f(tag_t, std::integral_constant<int, 8>());
-    });
+    return by_type(dtype, [&](auto tag_t) { return by_int<2, 4, 8>(P, [&](auto tag_p) { return f(tag_t, tag_p); }); });
 }
 
 // lanes per query of the fused sampler for head rows of D elements, 0 when it does not serve them
@@ -319,12 +315,13 @@ int mmfs_deform_plan_forward(int dtype, const void *off, const void *logit, int6
     if (rc) return rc;
     const int64_t items = N * Lq * H;
     if (items == 0) return MMFS_OK;
-    if (!off || !logit || !ref || !shapes || !loc || !attn) return MMFS_E_NULLPTR;
+    // (two phases: the outputs' alignment is looked at after the rows of the inputs)
+    int rr = check_tensors({{off, 1}, {logit, 1}, {ref, 1}, {shapes, 1}, {loc, 1}, {attn, 1}});
+    if (rr) return rr;
     const int es = elem_size(dtype);
-    int rr;
-    if ((rr = heads_rows(ld_off, H * L * P * 2, off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, logit, P, es)))
+    if ((rr = heads_rows(ld_off, H * L * P * 2, off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, logit, P, es)) ||
+        (rr = check_tensors({{loc, 16}, {attn, 16}})))
         return rr;
-    if ((uintptr_t)loc % 16 || (uintptr_t)attn % 16) return MMFS_E_ALIGN;
     d.ld_off = (int)ld_off; d.ld_att = (int)ld_att;
     const int ipb = kThreads / d.G;
     const unsigned blocks = (unsigned)((items + ipb - 1) / ipb);
@@ -349,12 +346,12 @@ int mmfs_deform_plan_backward(int dtype, const void *grad_loc, const void *grad_
     if (rc) return rc;
     const int64_t items = N * Lq * H;
     if (items == 0) return MMFS_OK;
-    if (!grad_loc || !grad_attn || !attn || !ref || !shapes || !grad_off || !grad_logit) return MMFS_E_NULLPTR;
+    int rr = check_tensors({{grad_loc, 1}, {grad_attn, 1}, {attn, 1}, {ref, 1}, {shapes, 1}, {grad_off, 1}, {grad_logit, 1}});
+    if (rr) return rr;
     const int es = elem_size(dtype);
-    int rr;
-    if ((rr = heads_rows(ld_off, H * L * P * 2, grad_off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, grad_logit, P, es)))
+    if ((rr = heads_rows(ld_off, H * L * P * 2, grad_off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, grad_logit, P, es)) ||
+        (rr = check_tensors({{grad_loc, 16}, {grad_attn, 16}, {attn, 16}})))
         return rr;
-    if ((uintptr_t)grad_loc % 16 || (uintptr_t)grad_attn % 16 || (uintptr_t)attn % 16) return MMFS_E_ALIGN;
     d.ld_off = (int)ld_off; d.ld_att = (int)ld_att;
     const int ipb = kThreads / d.G;
     const unsigned blocks = (unsigned)((items + ipb - 1) / ipb);
@@ -383,9 +380,8 @@ int mmfs_deform_sample_forward(int dtype, const void *value, const int64_t *shap
     const int es = elem_size(dtype);
     const int lpi = sampler_lpi(es, D);
     if (!lpi || S == 0 || S * H * D * (int64_t)es > kMaxSlabBytes) return MMFS_E_UNSUPPORTED;
-    if (!value || !shapes || !start || !off || !logit || !ref || !out) return MMFS_E_NULLPTR;
-    if (((uintptr_t)value | (uintptr_t)out) % 16) return MMFS_E_ALIGN;
-    int rr;
+    int rr = check_tensors({{value, 16}, {out, 16}, {shapes, 1}, {start, 1}, {off, 1}, {logit, 1}, {ref, 1}});
+    if (rr) return rr;
     if ((rr = heads_rows(ld_off, H * L * P * 2, off, 2 * P, es)) || (rr = heads_rows(ld_att, H * L * P, logit, P, es)))
         return rr;
     pd.ld_off = (int)ld_off; pd.ld_att = (int)ld_att;
@@ -407,13 +403,7 @@ int mmfs_deform_sample_forward(int dtype, const void *value, const int64_t *shap
                                (const T *)value, shapes, start, (const T *)off, (const T *)logit, ref, (T *)out, dd, pd);
             return (int)hipGetLastError();
         };
-        switch (lpi) {
-            case 2: return go(std::integral_constant<int, 2>());
-            case 4: return go(std::integral_constant<int, 4>());
-            case 8: return go(std::integral_constant<int, 8>());
-            case 16: return go(std::integral_constant<int, 16>());
-            default: return go(std::integral_constant<int, 32>());
-        }
+        return by_int<2, 4, 8, 16, 32>(lpi, go);
     });
 }
 

@@ -418,8 +418,7 @@ int mmfs_dwconv_tokens_forward(int dtype, const void *x, const void *weight, con
     ConvPlan p;
     const int rc = make_plan(dtype, level_hw, B, N, C, L, act, &p);
     if (rc || p.empty) return rc;
-    if (!x || !weight || !out) return MMFS_E_NULLPTR;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)out | (uintptr_t)pre) % 16) return MMFS_E_ALIGN;
+    if (const int rt = check_tensors({{x, 16}, {weight, 16}, maybe(bias, 16), {out, 16}, maybe(pre, 16)})) return rt;
     const unsigned blocks = (unsigned)((p.fwd_total + kThreads - 1) / kThreads);
     return by_type(dtype, [&](auto tag) {
         typedef decltype(tag) T;
@@ -451,11 +450,10 @@ int mmfs_dwconv_tokens_backward(int dtype, const void *grad_out, const void *x, 
     ConvPlan p;
     const int rc = make_plan(dtype, level_hw, B, N, C, L, act, &p);
     if (rc || p.empty) return rc;
-    if (!grad_out || !x || !weight || !grad_x || !grad_weight || !workspace || (act == MMFS_DWCONV_ACT_GELU && !pre))
-        return MMFS_E_NULLPTR;
-    if (((uintptr_t)grad_out | (uintptr_t)x | (uintptr_t)pre | (uintptr_t)weight | (uintptr_t)grad_x | (uintptr_t)workspace) % 16 ||
-        ((uintptr_t)grad_weight | (uintptr_t)grad_bias) % (uintptr_t)elem_size(dtype))
-        return MMFS_E_ALIGN;
+    const int es = elem_size(dtype);
+    if (const int rt = check_tensors({{grad_out, 16}, {x, 16}, {pre, 16, act == MMFS_DWCONV_ACT_GELU}, {weight, 16}, {grad_x, 16},
+                                      {workspace, 16}, {grad_weight, es}, maybe(grad_bias, es)}))
+        return rt;
     const dim3 grid((unsigned)p.bwd_blocks, (unsigned)((p.CL + p.CLB - 1) / p.CLB));
     const int E = (int)(kSums * C);
     return by_type(dtype, [&](auto tag) {
