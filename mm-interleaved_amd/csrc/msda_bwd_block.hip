@@ -27,6 +27,7 @@
 #include "msda_plan.h"
 #include <vector>
 #include <cstdlib>
+#include "msda_prof.h"      // (the readout alone: the sort's clock is an instrument of its own, SPROF below)
 
 namespace mmfs {
 
@@ -1523,12 +1524,7 @@ extern "C" int mmfs_msda_plan_selfcheck(int64_t Hl, int64_t Wl, int nt_min)
 #ifdef MMFS_PROFILE_SORT
 extern "C" int mmfs_debug_sort_profile(unsigned long long *out, int reset)
 {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(mmfs::g_sort_prof), 64 * sizeof(unsigned long long));
-    if (e == hipSuccess && reset) {
-        unsigned long long z[64] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_sort_prof), z, sizeof z);
-    }
-    return (int)e;
+    return mmfs::prof_copyout<64>(HIP_SYMBOL(mmfs::g_sort_prof), out, reset);
 }
 extern "C" int mmfs_debug_sort_timeline(unsigned long long *out)
 {

@@ -31,6 +31,13 @@
 #include "msda_env.h"
 #include "msda_launch.h"
 #include <type_traits>
+#ifdef MMFS_PROFILE_TS
+#define MMFS_PROF_COUNTERS g_ts_prof
+#endif
+#define MMFS_PROF_SLOTS 32768
+#define MMFS_PROF_N 12
+#define MMFS_PROF_LANE (threadIdx.x == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 namespace blk {
@@ -86,21 +93,9 @@ template <int D> struct TsGeom {
 
 // Development aid (tools/exp_build1.sh tsprof msda_bwd_taps_sorted "-DMMFS_PROFILE_TS"; tools/ts_prof.py): shader clocks per
 // phase of a work item, summed over items, read back with mmfs_debug_ts_profile().
-#ifdef MMFS_PROFILE_TS
 }  // namespace
-constexpr int kTsProfSlots = 32768;
-__device__ unsigned long long g_ts_prof[kTsProfSlots * 12];      // one row per workgroup (mod kTsProfSlots): no contended atomics
+MMFS_PROF_STORAGE;
 namespace {
-#define TSPROF_DECL unsigned long long tsp_c = __builtin_readcyclecounter(), tsp_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define TSPROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); tsp_t[i] += tn - tsp_c; tsp_c = tn; } while (0)
-#define TSPROF_COUNT(i, v) do { tsp_t[i] += (unsigned long long)(v); } while (0)
-#define TSPROF_FLUSH() do { if (threadIdx.x == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_ts_prof[(blockIdx.x % kTsProfSlots) * 12 + i_], tsp_t[i_]); } while (0)
-#else
-#define TSPROF_DECL do {} while (0)
-#define TSPROF(i) do {} while (0)
-#define TSPROF_COUNT(i, v) do {} while (0)
-#define TSPROF_FLUSH() do {} while (0)
-#endif
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -151,14 +146,14 @@ __device__ __forceinline__ void taps_item(const T *__restrict__ value, const T *
     typedef DotMma<T> M;
     unsigned char *rows = lds, *recs = lds + G::ROWS_BYTES, *dots = recs + G::REC_BYTES;
     const int lane = threadIdx.x;
-    TSPROF_DECL;
+    PROF_DECL;
     const int Hl = (int)(td.hw >> 16), Wl = (int)(td.hw & 0xffffu);
     const int by = (int)(td.byx >> 16), bx = (int)(td.byx & 0xffffu);
     int pre[6];
     pre[0] = 0;
 #pragma unroll
     for (int r = 0; r < 5; ++r) pre[r + 1] = pre[r] + xd.ocnt[r];
-    if (__builtin_amdgcn_readfirstlane(pre[5]) >= 0) TSPROF(0);     // descriptors arrived
+    if (__builtin_amdgcn_readfirstlane(pre[5]) >= 0) PROF(0);     // descriptors arrived
     const int n = pre[5];
     const int parts = (int)td.parts > 0 ? (int)td.parts : 1;
     const int e0 = (int)((int64_t)n * it.part / parts), e1 = (int)((int64_t)n * (it.part + 1) / parts);
@@ -166,7 +161,7 @@ __device__ __forceinline__ void taps_item(const T *__restrict__ value, const T *
     if (cnt <= 0) return;
     const int nks = (cnt + kKS - 1) / kKS;
     const int rounds = (nks + 3) / 4;
-    TSPROF_COUNT(8, 1); TSPROF_COUNT(9, rounds); TSPROF_COUNT(10, nks); TSPROF_COUNT(11, cnt);
+    PROF_COUNT(8, 1); PROF_COUNT(9, rounds); PROF_COUNT(10, nks); PROF_COUNT(11, cnt);
 
     const int n16 = lane & 15, j = lane >> 4;                      // this lane's record of a step / its pixel row of the 5x5
     const int y00 = kTB * by - 1, x00 = kTB * bx - 1;              // the 5x5's first pixel
@@ -360,10 +355,10 @@ __device__ __forceinline__ void taps_item(const T *__restrict__ value, const T *
         if (4 * jb + 3 < nks) multiply(jb, S3{});
     }
     flush();
-    TSPROF(3);                                                 // rounds
+    PROF(3);                                                 // rounds
     MMFS_TS_WAIT_VM(0);                                        // (requests past the end of the list: the LDS is another item's soon)
-    TSPROF(4);
-    TSPROF_FLUSH();
+    PROF(4);
+    PROF_FLUSH();
 }
 
 // One wave per work item, the grid and the item -> workgroup order of msda_bwd_tile_reduce: a (b, h) slice's workgroups are
@@ -434,16 +429,7 @@ hipError_t dispatch_taps(const void *value, const void *go, void *gl, void *ga, 
 #ifdef MMFS_PROFILE_TS
 extern "C" int mmfs_debug_ts_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[kTsProfSlots * 12];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ts_prof), sizeof(host));
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    for (int s = 0; s < kTsProfSlots; ++s)
-        for (int i = 0; i < 12; ++i) out[i] += host[s * 12 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ts_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N, 16>(HIP_SYMBOL(g_ts_prof), out, reset);
 }
 #endif
 }  // namespace blk

@@ -43,6 +43,13 @@
 #include "msda_launch.h"
 #include <cstdlib>
 #include <type_traits>
+#ifdef MMFS_PROFILE_TILE
+#define MMFS_PROF_COUNTERS g_tile_prof
+#endif
+#define MMFS_PROF_SLOTS 32768
+#define MMFS_PROF_N 12
+#define MMFS_PROF_LANE (threadIdx.x == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 namespace blk {
@@ -111,23 +118,9 @@ template <int D> struct TileGeom {
 
 // Development aid (tools/exp_build.sh tprof "-DMMFS_PROFILE_TILE"): shader clocks per phase of a work
 // item, summed over items, read back with mmfs_debug_tile_profile().
-#ifdef MMFS_PROFILE_TILE
 }  // namespace
-constexpr int kProfSlots = 32768;
-__device__ unsigned long long g_tile_prof[kProfSlots * 12];     // one row per workgroup (mod kProfSlots): no contended atomics
+MMFS_PROF_STORAGE;
 namespace {
-// (the deltas are kept in registers and flushed once, at the end of the item: an atomic per phase would sit
-// in the very vmcnt queue the phases wait on)
-#define TPROF_DECL unsigned long long tprof_c = __builtin_readcyclecounter(), tprof_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define TPROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); tprof_t[i] += tn - tprof_c; tprof_c = tn; } while (0)
-#define TPROF_COUNT(i, v) do { tprof_t[i] += (unsigned long long)(v); } while (0)
-#define TPROF_FLUSH() do { if (threadIdx.x == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_tile_prof[(blockIdx.x % kProfSlots) * 12 + i_], tprof_t[i_]); } while (0)
-#else
-#define TPROF_FLUSH() do {} while (0)
-#define TPROF_DECL do {} while (0)
-#define TPROF(i) do {} while (0)
-#define TPROF_COUNT(i, v) do {} while (0)
-#endif
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -175,7 +168,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
     typedef TileMma<T> M;
     unsigned char *rows = lds, *recs = lds + G::ROWS_BYTES, *atile = recs + G::REC_BYTES;
     const int lane = threadIdx.x;
-    TPROF_DECL;
+    PROF_DECL;
     const int Hl = (int)(td.hw >> 16), Wl = (int)(td.hw & 0xffffu);
     const int by = (int)(td.byx >> 16), bx = (int)(td.byx & 0xffffu);
     int pre[6];
@@ -188,8 +181,8 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
     const int cnt = e1 > e0 ? e1 - e0 : 0;                        // records of this item
     const int nks = (cnt + kKS - 1) / kKS;
     const int rounds = (nks + 3) / 4;
-    if (__builtin_amdgcn_readfirstlane(n) >= 0) TPROF(0);          // descriptor arrived
-    TPROF_COUNT(8, 1); TPROF_COUNT(9, rounds); TPROF_COUNT(10, nks);
+    if (__builtin_amdgcn_readfirstlane(n) >= 0) PROF(0);          // descriptor arrived
+    PROF_COUNT(8, 1); PROF_COUNT(9, rounds); PROF_COUNT(10, nks);
 
     const uint32_t HDB = (uint32_t)(d.H * d.D) * (uint32_t)sizeof(T);            // bytes between consecutive queries
     const T *gslice = grad_out + ((int64_t)it.b * d.Nq * d.H + it.h) * d.D;
@@ -300,11 +293,11 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
         // prologue: recs(0) | rows(0)
         issue_records(0);
         MMFS_WAIT_VM(0);
-        TPROF(1);                                                 // LDS cleared, first records landed
+        PROF(1);                                                 // LDS cleared, first records landed
         issue_rows(0, S0{});
         for (int j = 0; j < rounds; ++j) {
             MMFS_WAIT_VM(0);
-            if (j == 0) TPROF(2);                                 // first rows landed
+            if (j == 0) PROF(2);                                 // first rows landed
             issue_rows(j, S1{});                                  // rows(4j + 1)
             issue_records(j + 1);
             if (4 * j < nks) multiply(j, S0{});
@@ -318,9 +311,9 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
             issue_rows(j + 1, S0{});                              // rows(4j + 4): first step of batch j + 1
             if (4 * j + 3 < nks) multiply(j, S3{});
         }
-        TPROF(3);                                                 // rounds
+        PROF(3);                                                 // rounds
         MMFS_WAIT_VM(0);                                          // (requests past the end of the list)
-        TPROF(4);
+        PROF(4);
     }
 
     // ---- epilogue: hi + lo rows; lane pairs exchange one value so that every lane holds whole dwords
@@ -411,11 +404,11 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
 #ifdef MMFS_PROFILE_TILE
     {   // epilogue clocks and counts by kind of item: whole blocks / parts that leave a partial tile
         const unsigned long long tn = __builtin_readcyclecounter();
-        if (it.partial_out) { tprof_t[6] += tn - tprof_c; tprof_t[7] += 1; } else { tprof_t[11] += tn - tprof_c; }
+        if (it.partial_out) { prof_t[6] += tn - prof_c; prof_t[7] += 1; } else { prof_t[11] += tn - prof_c; }
     }
 #endif
-    TPROF(5);                                                     // epilogue issued
-    TPROF_FLUSH();
+    PROF(5);                                                     // epilogue issued
+    PROF_FLUSH();
 }
 
 // One wave per work item.  A (b, h) slice's workgroups are consecutive in the dispatch order of their XCD (h is the
@@ -489,16 +482,7 @@ hipError_t dispatch_tile(const void *go, void *gv, const TileReduceArgs &a, cons
 #ifdef MMFS_PROFILE_TILE
 extern "C" int mmfs_debug_tile_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[mmfs::blk::kProfSlots * 12];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(mmfs::blk::g_tile_prof), sizeof(host));
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    for (int s = 0; s < mmfs::blk::kProfSlots; ++s)
-        for (int i = 0; i < 12; ++i) out[i] += host[s * 12 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::blk::g_tile_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N, 16>(HIP_SYMBOL(mmfs::blk::g_tile_prof), out, reset);
 }
 #endif
 

@@ -27,6 +27,13 @@
 #include "msda_plan.h"
 #include <cstring>
 #include <cstdlib>
+#ifdef MMFS_PROFILE_DENSE
+#define MMFS_PROF_COUNTERS g_dense_prof
+#endif
+#define MMFS_PROF_SLOTS 4
+#define MMFS_PROF_N 8
+#define MMFS_PROF_LANE (threadIdx.x == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 
@@ -76,18 +83,9 @@ __device__ __forceinline__ int mfma_row(int reg, int lane) { return (reg & 3) + 
 
 // Development aid (tools/exp_build.sh dense_prof "-DMMFS_PROFILE_DENSE"): shader clocks per phase,
 // summed over workgroups (thread 0 of each), read back with mmfs_debug_dense_profile().
-#ifdef MMFS_PROFILE_DENSE
 }  // namespace
-__device__ unsigned long long g_dense_prof[32];
+MMFS_PROF_STORAGE;
 namespace {
-#define PROF_DECL unsigned long long prof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long prof_c = __builtin_readcyclecounter()
-#define PROF(i) do { const unsigned long long prof_n = __builtin_readcyclecounter(); prof_t[i] += prof_n - prof_c; prof_c = prof_n; } while (0)
-#define PROF_END(base) do { if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_dense_prof[(base) + i], prof_t[i]); } while (0)
-#else
-#define PROF_DECL do {} while (0)
-#define PROF(i) do {} while (0)
-#define PROF_END(base) do {} while (0)
-#endif
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -255,7 +253,7 @@ msda_taps_coarse(const T *__restrict__ value, const T *__restrict__ loc, const T
         }
     }
     if (have_pending) lookups(pend, pxy, pa, G[buf ^ 1]);
-    PROF_END(0);
+    PROF_FLUSH_ROW(0);
     // ---- the grad_value half's opening launch, hosted here when one call runs both halves (msda_plan.h): the first
     // workgroup clears the sort's cursors and plans; the product tiles serve as its scratch
     if (job.cursor_words > 0 && blockIdx.x == 0) {
@@ -384,11 +382,6 @@ hipError_t backward_taps_coarse(int dtype, const void *value, const void *loc, c
 #ifdef MMFS_PROFILE_DENSE
 extern "C" int mmfs_debug_dense_profile(unsigned long long *out, int reset)
 {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(mmfs::g_dense_prof), sizeof(unsigned long long) * 32);
-    if (e == hipSuccess && reset) {
-        unsigned long long z[32] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_dense_prof), z, sizeof(z));
-    }
-    return (int)e;
+    return mmfs::prof_copyout<MMFS_PROF_SLOTS * MMFS_PROF_N>(HIP_SYMBOL(mmfs::g_dense_prof), out, reset);
 }
 #endif

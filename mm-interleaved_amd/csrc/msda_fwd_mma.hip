@@ -42,6 +42,13 @@
 #include "msda_env.h"
 #include "msda_launch.h"
 #include <cstdlib>
+#ifdef MMFS_PROFILE_FWD
+#define MMFS_PROF_COUNTERS g_fwd_prof
+#endif
+#define MMFS_PROF_SLOTS 4096
+#define MMFS_PROF_N 8
+#define MMFS_PROF_LANE ((threadIdx.x & 63) == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 
@@ -49,19 +56,7 @@ using namespace mma;
 
 // Development aid (tools/exp_build.sh fprof "-DMMFS_PROFILE_FWD"; tools/fwd_prof.py): shader clocks per phase of a
 // wave, summed over the waves of a workgroup slot, read back with mmfs_debug_fwd_profile().
-#ifdef MMFS_PROFILE_FWD
-constexpr int kFProfSlots = 4096;
-__device__ unsigned long long g_fwd_prof[kFProfSlots * 8];
-#define FPROF_DECL unsigned long long fprof_c = __builtin_readcyclecounter(), fprof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define FPROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); fprof_t[i] += tn - fprof_c; fprof_c = tn; } while (0)
-#define FPROF_COUNT(i, v) do { fprof_t[i] += (unsigned long long)(v); } while (0)
-#define FPROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_fwd_prof[(blockIdx.x % kFProfSlots) * 8 + i_], fprof_t[i_]); } while (0)
-#else
-#define FPROF_DECL do {} while (0)
-#define FPROF(i) do {} while (0)
-#define FPROF_COUNT(i, v) do {} while (0)
-#define FPROF_FLUSH() do {} while (0)
-#endif
+MMFS_PROF_STORAGE;
 
 template <typename T, int D>
 __global__ void __launch_bounds__(kMmaThreads)
@@ -82,11 +77,11 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    FPROF_DECL;
+    PROF_DECL;
     const int L = d.L;
     const int64_t HD = (int64_t)d.H * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
-    build_level_table<D>(tab, img, shapes, start, L, tid, img_budget);
+    build_level_table<PitchedImage<D, true>>(tab, img, shapes, start, L, tid, img_budget);
     // One run of queries per workgroup, dealt by the dispatcher in the order run -> (b, h, queries) with h = run mod H
     // (a head's slab stays in one XCD's L2).  The loop serves persistent workgroups (persistent_grid, msda_mma_common.h).
     for (int run = blockIdx.x; run < n_runs; run += gridDim.x) {
@@ -143,8 +138,8 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     prefetch(0);
     // ---- the run's image
     if (run != (int)blockIdx.x) __syncthreads();                          // every wave is done with the previous image
-    fill_image<D, true>(tab, img, rsrc, row_bytes, L, d.S, tid);          // channel-permuted (header)
-    FPROF(0);                                                             // barrier + image writes (incl. waiting for the slowest wave)
+    fill_image<PitchedImage<D, true>>(tab, img, rsrc, row_bytes, L, d.S, tid);          // channel-permuted (header)
+    PROF(0);                                                             // barrier + image writes (incl. waiting for the slowest wave)
     float acc[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
@@ -230,7 +225,7 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                 live |= (uint32_t)(bl | (bl >> 16) | (bl >> 32) | (bl >> 48)) & 0xffffu;
             }
             wave_sync();
-            FPROF(1);                                                     // stage
+            PROF(1);                                                     // stage
 
             // ---- LDS-resident levels on the matrix cores: batches of 8 samples per query
             auto mma_phase = [&]() {
@@ -336,10 +331,10 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                     issue(r0, g0); issue(r1, g1); issue(r2, g2); issue(r3, g3);
                     prefetch(step + 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    FPROF(2);                                             // first issues + next step's requests
+                    PROF(2);                                             // first issues + next step's requests
                     mma_phase();
                     __builtin_amdgcn_sched_barrier(0);
-                    FPROF(3);                                             // matrix-core phase
+                    PROF(3);                                             // matrix-core phase
                     for (int i = 4; i < n_live; i += 4) {
                         consume(r0, g0); issue(r0, g0);
                         consume(r1, g1); issue(r1, g1);
@@ -347,7 +342,7 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                         consume(r3, g3); issue(r3, g3);
                     }
                     consume(r0, g0); consume(r1, g1); consume(r2, g2); consume(r3, g3);
-                    FPROF(4);                                             // gather loop
+                    PROF(4);                                             // gather loop
                 } else {
                     prefetch(step + 1);
                     __builtin_amdgcn_sched_barrier(0);
@@ -368,7 +363,7 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                         consume(rawA, gA);
                         consume(rawB, gB);
                     }
-                    FPROF(5);                                             // the general path, whole
+                    PROF(5);                                             // the general path, whole
                 }
             }
         }
@@ -389,12 +384,12 @@ msda_fwd_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes,
             }
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-            FPROF(6);                                                     // store
+            PROF(6);                                                     // store
         }
     }
-    FPROF_COUNT(7, n_steps);
+    PROF_COUNT(7, n_steps);
     }   // runs
-    FPROF_FLUSH();
+    PROF_FLUSH();
 }
 
 // ---------------------------------------------------------------- launcher
@@ -403,33 +398,21 @@ static hipError_t launch_mma(const void *value, const int64_t *shapes, const int
                              const void *loc, const void *attn, void *out, Dims d, hipStream_t st)
 {
     typedef MmaGeom<D> G;
-    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_mma<T, D>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
-    if (once != hipSuccess) return once;
-    const int env_kb = knob_int(K_FWD_MMA_LDS_KB, 0);      // tuning / debugging
-    const int lds_total = env_kb > 0 ? std::min(kLdsTotal, std::max(G::IMG0 + 1024, env_kb * 1024)) : kLdsTotal;
+    if (const hipError_t e = allow_full_lds<&msda_fwd_mma<T, D>>()) return e;
+    const int lds_total = lds_bytes(K_FWD_MMA_LDS_KB, G::IMG0);
     // queries per workgroup: the image fill (up to IMG_BUDGET bytes through the texture path) is paid per workgroup,
     // so runs are long; but the grid should still be a few workgroups per CU for the tail
-    const int env_q = knob_int(K_FWD_MMA_QPW, 0);
-    const int unit = kMmaWaves * G::QPW;
-    const int q_per_wg = pick_queries_per_run(d, unit, env_q);       // (256, or shorter runs for few queries: msda_mma_common.h)
-    d.q_tiles = (d.Nq + q_per_wg - 1) / q_per_wg;
-    const int64_t runs = (int64_t)d.B * d.q_tiles * d.H;
-    if (runs > 0x7fffffffLL) return hipErrorInvalidValue;
-    const int grid = (int)persistent_grid(runs, d.H);                       // (one workgroup per CU when there are many runs, else = runs)
-    hipLaunchKernelGGL((msda_fwd_mma<T, D>), dim3((unsigned)grid), dim3(kMmaThreads), lds_total, st,
-                       (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, q_per_wg,
-                       lds_total - G::IMG0, (int)runs);
-    return hipGetLastError();
+    const int q_per_wg = pick_queries_per_run(d, kMmaWaves * G::QPW, knob_int(K_FWD_MMA_QPW, 0));   // (256, or shorter runs for few queries: msda_mma_common.h)
+    return launch_runs(d, q_per_wg, 1, [&](const Dims &dq, dim3 grid, int runs) {
+        hipLaunchKernelGGL((msda_fwd_mma<T, D>), grid, dim3(kMmaThreads), lds_total, st,
+                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, dq, q_per_wg,
+                           lds_total - G::IMG0, runs);
+    });
 }
 
 bool fwd_mma_supported(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return false;
-    if (d.D != 128 && d.D != 64) return false;
-    if (d.L > kMmaMaxLevels || d.K <= 0) return false;
-    if ((int64_t)d.Nq * d.H * d.K >= (1LL << 30)) return false;            // 32-bit sample offsets inside a (b, h) slab
-    return (int64_t)d.S * d.H * d.D * 2 <= kMaxSlabBytes;
+    return (d.D == 128 || d.D == 64) && resident_shape_supported(dtype, d);
 }
 
 bool fwd_mma_applies(int dtype, const Dims &d)
@@ -450,12 +433,11 @@ bool fwd_mma_applies(int dtype, const Dims &d)
 hipError_t forward_mma(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
                        const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
 {
-    if (dtype == 1) {
-        if (d.D == 128) return launch_mma<half_t, 128>(value, shapes, start, loc, attn, out, d, st);
-        return launch_mma<half_t, 64>(value, shapes, start, loc, attn, out, d, st);
-    }
-    if (d.D == 128) return launch_mma<bf16_t, 128>(value, shapes, start, loc, attn, out, d, st);
-    return launch_mma<bf16_t, 64>(value, shapes, start, loc, attn, out, d, st);
+    return by_half_type(dtype, [&](auto t) {
+        return by_int<128, 64>(d.D, [&](auto w) {
+            return launch_mma<decltype(t), decltype(w)::value>(value, shapes, start, loc, attn, out, d, st);
+        });
+    });
 }
 
 }  // namespace mmfs
@@ -463,15 +445,6 @@ hipError_t forward_mma(int dtype, const void *value, const int64_t *shapes, cons
 #ifdef MMFS_PROFILE_FWD
 extern "C" int mmfs_debug_fwd_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[mmfs::kFProfSlots * 8];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(mmfs::g_fwd_prof), sizeof(host));
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    for (int s = 0; s < mmfs::kFProfSlots; ++s)
-        for (int i = 0; i < 8; ++i) out[i] += host[s * 8 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_fwd_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N>(HIP_SYMBOL(mmfs::g_fwd_prof), out, reset);
 }
 #endif

@@ -45,6 +45,13 @@
 #include "msda_launch.h"
 #include <cstdlib>
 #include <type_traits>
+#ifdef MMFS_PROFILE_Q8
+#define MMFS_PROF_COUNTERS g_q8_prof
+#endif
+#define MMFS_PROF_SLOTS 4096
+#define MMFS_PROF_N 8
+#define MMFS_PROF_LANE ((threadIdx.x & 63) == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 
@@ -52,19 +59,7 @@ using namespace mma;
 
 // Development aid (tools/exp_build.sh q8prof "-DMMFS_PROFILE_Q8"; tools/q8_prof.py): shader clocks per phase of a wave,
 // summed over waves per workgroup slot, read back with mmfs_debug_q8_profile().
-#ifdef MMFS_PROFILE_Q8
-constexpr int kQProfSlots = 4096;
-__device__ unsigned long long g_q8_prof[kQProfSlots * 8];
-#define QPROF_DECL unsigned long long qprof_c = __builtin_readcyclecounter(), qprof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define QPROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); qprof_t[i] += tn - qprof_c; qprof_c = tn; } while (0)
-#define QPROF_COUNT(i, v) do { qprof_t[i] += (unsigned long long)(v); } while (0)
-#define QPROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_q8_prof[(blockIdx.x % kQProfSlots) * 8 + i_], qprof_t[i_]); } while (0)
-#else
-#define QPROF_DECL do {} while (0)
-#define QPROF(i) do {} while (0)
-#define QPROF_COUNT(i, v) do {} while (0)
-#define QPROF_FLUSH() do {} while (0)
-#endif
+MMFS_PROF_STORAGE;
 
 
 // Development aid (tools/debug/q8_probe.py; -DQ8_PROBE): at the end of a pass's staging every lane reads back what it stored for
@@ -109,37 +104,28 @@ static_assert(8 * kRec <= kScratch, "records of a pass");
 // pixels per line of a W-pixel-wide level in the image: W + at least two zero pixels, = 2 (mod 4)
 __host__ __device__ __forceinline__ int line_pixels(int W) { return W + 2 + ((4 - (W & 3)) & 3); }
 
-// Level table -> LDS; which levels live in the image (smallest first, ties: lower index, while they fit); the image
-// cleared once (its borders stay zero: the fills only write the pixels).  Every thread; ends with a barrier.
-__device__ __forceinline__ void build_table(int *tab, unsigned char *smem, const int64_t *__restrict__ shapes,
-                                            const int64_t *__restrict__ start, int L, int K, int P, int tid, int lds_total)
+// The image (placement: build_level_table, fill: fill_image, msda_mma_common.h): a level's slice with a border of zero
+// pixels -- Hl + 2 lines of line_pixels(Wl) pixels of kRB bytes -- in natural channel order; bases count from the
+// workgroup's LDS, where the image starts at kImg0.  The image is cleared once per workgroup (its borders stay zero: the
+// fills only write the pixels).
+struct Image {
+    static constexpr int kStride = kTab, kMaxSide = 2048, kFirst = kImg0, kPieces = kRB / 16;
+    static constexpr bool kZeroEarly = true;
+    static constexpr int kBorderLines = 2, kUnitBytes = kRB, kBlock = 1;
+    static constexpr bool kPaddedLines = true, kSlot4InBytes = false;
+    static __device__ __forceinline__ int line(int Wl) { return line_pixels(Wl); }
+    static __device__ __forceinline__ void zero(unsigned char *smem, int tid, int lds_total)
+    {
+        for (int i = tid; i < (lds_total - kImg0) / 16; i += kMmaThreads)
+            reinterpret_cast<uint4 *>(smem + kImg0)[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    static __device__ __forceinline__ int dst(int base, int y, int x, int lw, int c) { return base + ((y + 1) * lw + x + 1) * kRB + 16 * c; }
+    static __device__ __forceinline__ void store(unsigned char *at, const uint4 &raw) { *reinterpret_cast<uint4 *>(at) = raw; }
+};
+
+// What the staging needs of sample index k's level, as it needs it (behind build_level_table).  Every thread; ends with a barrier.
+__device__ __forceinline__ void build_ktab(const int *tab, unsigned char *smem, int K, int P, int tid)
 {
-    for (int l = tid; l < L; l += kMmaThreads) {
-        const int Hl = (int)shapes[2 * l], Wl = (int)shapes[2 * l + 1];
-        int bytes = (Hl > 0 && Wl > 0) ? 1 << 24 : 0;                   // "never fits"; an empty level takes no room
-        int lw = 0;
-        if (Hl > 0 && Wl > 0 && Hl <= 2048 && Wl <= 2048) {
-            lw = line_pixels(Wl);
-            const int64_t bb = (int64_t)(Hl + 2) * lw * kRB;
-            if (bb < (1 << 24)) bytes = (int)bb;
-        }
-        tab[kTab * l] = Hl; tab[kTab * l + 1] = Wl; tab[kTab * l + 2] = (int)start[l];
-        tab[kTab * l + 4] = lw; tab[kTab * l + 5] = bytes;
-    }
-    for (int i = tid; i < (lds_total - kImg0) / 16; i += kMmaThreads)
-        reinterpret_cast<uint4 *>(smem + kImg0)[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-    for (int l = tid; l < L; l += kMmaThreads) {
-        const int px = tab[kTab * l] * tab[kTab * l + 1], bytes = tab[kTab * l + 5];
-        int cum = 0;
-        for (int l2 = 0; l2 < L; ++l2) {
-            const int px2 = tab[kTab * l2] * tab[kTab * l2 + 1];
-            if (px2 < px || (px2 == px && l2 <= l)) cum += tab[kTab * l2 + 5];
-        }
-        tab[kTab * l + 3] = (px > 0 && kImg0 + cum <= lds_total) ? kImg0 + cum - bytes : -1;      // (byte offset in the workgroup's LDS)
-    }
-    __syncthreads();
-    // what the staging needs of sample index k's level, as it needs it
     uint4 *ktab = reinterpret_cast<uint4 *>(smem + kTabBytes);
     for (int k = tid; k < K && k < kMaxK; k += kMmaThreads) {
         const int l = k / P;
@@ -147,43 +133,6 @@ __device__ __forceinline__ void build_table(int *tab, unsigned char *smem, const
         ktab[2 * k] = make_uint4(__float_as_uint((float)Hl), __float_as_uint((float)Wl), (uint32_t)tab[kTab * l + 3],
                                  (uint32_t)(tab[kTab * l + 4] * kRB));
         ktab[2 * k + 1] = make_uint4((uint32_t)tab[kTab * l + 2], (uint32_t)Wl, (uint32_t)Hl, 0u);
-    }
-    __syncthreads();
-}
-
-// Resident levels' slices global -> LDS, natural channel order, four 16-byte pieces in flight per lane.  Ends with a barrier.
-__device__ __forceinline__ void fill_image(const int *tab, unsigned char *smem, __amdgpu_buffer_rsrc_t rsrc,
-                                           uint32_t row_bytes, int L, int S, int tid)
-{
-    constexpr int NB = 4;
-    for (int l = 0; l < L; ++l) {
-        const int base = tab[kTab * l + 3];
-        if (base < 0) continue;
-        const int Hl = tab[kTab * l], Wl = tab[kTab * l + 1], st = tab[kTab * l + 2], lw = tab[kTab * l + 4];
-        const int units = Hl * Wl * (kRB / 16);
-        const float inv_w = 1.0f / (float)Wl;
-        for (int u0 = tid; u0 < units; u0 += NB * kMmaThreads) {
-            uint4 raw[NB];
-            int dst[NB];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                const int u = u0 + i * kMmaThreads;
-                dst[i] = -1;
-                raw[i] = make_uint4(0u, 0u, 0u, 0u);
-                if (u < units) {
-                    const int p = u >> 2, c = u & 3;
-                    int y = (int)((float)p * inv_w);                       // p / Wl for p < 2^22: a float guess, corrected
-                    y -= (y * Wl > p); y += ((y + 1) * Wl <= p);
-                    const int x = p - y * Wl;
-                    const uint32_t goff = (uint32_t)(st + p) < (uint32_t)S ? (uint32_t)(st + p) * row_bytes + (uint32_t)c * 16u : kOobOffset;
-                    raw[i] = buffer_load16(rsrc, goff);
-                    dst[i] = base + ((y + 1) * lw + x + 1) * kRB + 16 * c;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-                if (dst[i] >= 0) *reinterpret_cast<uint4 *>(smem + dst[i]) = raw[i];
-        }
     }
     __syncthreads();
 }
@@ -243,8 +192,9 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
     const int L = d.L, K = d.K;
     const int64_t HD = (int64_t)d.H * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
-    QPROF_DECL;
-    build_table(tab, smem, shapes, start, L, K, d.P, tid, lds_total);
+    PROF_DECL;
+    build_level_table<Image>(tab, smem, shapes, start, L, tid, lds_total);
+    build_ktab(tab, smem, K, d.P, tid);
 
     // (LDS addresses as plain 32-bit numbers: "smem + x" costs an add per use, the dynamic LDS starts where it starts)
     typedef __attribute__((address_space(3))) unsigned char lds_byte;
@@ -304,8 +254,8 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
     };
     prefetch(0, 0);
     if (run != (int)blockIdx.x) __syncthreads();                          // every wave is done with the previous image
-    fill_image(tab, smem, rsrc, row_bytes, L, d.S, tid);
-    QPROF(0);                                                             // table / barrier + image fill (incl. waiting for the slowest wave)
+    fill_image<Image>(tab, smem, rsrc, row_bytes, L, d.S, tid);
+    PROF(0);                                                             // table / barrier + image fill (incl. waiting for the slowest wave)
 
     for (int tile = 0; tile < n_tiles; ++tile) {
 #ifndef Q8_NO_SETPRIO
@@ -426,7 +376,7 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
         wave_sync();
         if (pass + 1 < n_pass) prefetch(tile, pass + 1); else prefetch(tile + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        QPROF(1);                                                         // stage
+        PROF(1);                                                         // stage
 
         // ---- resident K-blocks: 32 rows out of the image and two products (2 x 16 channels) each.  N K-blocks as ONE
         // straight-line sequence -- all record reads, then all transposing reads, then the products (two chains) -- so
@@ -506,18 +456,18 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
             if (gm) { i0 = take(); issue(i0, r0); }
             if (gm) { i1 = take(); issue(i1, r1); }
             __builtin_amdgcn_sched_barrier(0);
-            QPROF(2);                                                     // first row requests
+            PROF(2);                                                     // first row requests
             nibble(rm, std::integral_constant<int, 0>{});
             nibble(rm, std::integral_constant<int, 4>{});
             __builtin_amdgcn_sched_barrier(0);
-            QPROF(3);                                                     // resident K-blocks
-            QPROF_COUNT(6, __builtin_popcount(rm));
+            PROF(3);                                                     // resident K-blocks
+            PROF_COUNT(6, __builtin_popcount(rm));
             while (i0 >= 0) {
                 consume(i0, r0); i0 = -1;
                 if (gm) { i0 = take(); issue(i0, r0); }
                 if (i1 >= 0) { consume(i1, r1); i1 = -1; if (gm) { i1 = take(); issue(i1, r1); } }
             }
-            QPROF(4);                                                     // row gather
+            PROF(4);                                                     // row gather
         }
         }   // passes
 
@@ -566,11 +516,11 @@ msda_fwd_q8(const T *__restrict__ value, const int64_t *__restrict__ shapes, con
         wave_sync();
         // (the sums lay over the records' zero bytes)
         if (lane < 8) *reinterpret_cast<uint4 *>(smem + wrec + lane * kRec + 288) = make_uint4(0u, 0u, 0u, 0u);
-        QPROF(5);                                                         // epilogue
-        QPROF_COUNT(7, n_pass);
+        PROF(5);                                                         // epilogue
+        PROF_COUNT(7, n_pass);
     }   // tiles
     }   // runs
-    QPROF_FLUSH();
+    PROF_FLUSH();
 }
 
 // The host sees no level table (device pointers only): "every level's slice fits in the image" is judged from S -- a
@@ -586,22 +536,15 @@ static hipError_t launch_q8(const void *value, const int64_t *shapes, const int6
                             const void *loc, const void *attn, void *out, Dims d, hipStream_t st)
 {
     using namespace q8;
-    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_q8<T>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
-    if (once != hipSuccess) return once;
-    const int env_kb = knob_int(K_FWD_Q8_LDS_KB, 0);      // tuning / tests
-    const int lds_total = env_kb > 0 ? std::min(kLdsTotal, std::max(kImg0 + 1024, env_kb * 1024)) : kLdsTotal;
+    if (const hipError_t e = allow_full_lds<&msda_fwd_q8<T>>()) return e;
+    const int lds_total = lds_bytes(K_FWD_Q8_LDS_KB, kImg0);
     // Queries per run: the image fill (one pass over the resident levels' slices + the barrier around it: 14-19 k clocks
     // per wave, a quarter of a 512-query run at the LLM geometry, r04f) is paid per run, so runs are as long as the shape
     // allows while every CU still gets one: up to 1024 queries (longer runs put more (b, h) slabs of the row-gather
     // levels into an XCD's L2 at a time: r03bf).
     const int unit = kMmaWaves * kQT;
     const int n_slices = d.D / kCS;
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n > 0 ? n : 256;
-    }();
+    const int cus = device_cus();
     // (shapes whose levels do not all fit keep 512: at the LLM geometry with 4 images 1024 cost 258 us against 234)
     int q_per_run = q8_all_resident_likely(d) ? 1024 : 512;
     const int64_t units = (int64_t)d.B * d.H * n_slices;
@@ -609,23 +552,17 @@ static hipError_t launch_q8(const void *value, const int64_t *shapes, const int6
     const int env_q = knob_int(K_FWD_Q8_QPR, 0);
     if (env_q > 0) q_per_run = env_q;
     q_per_run = std::max(unit, (q_per_run + unit - 1) / unit * unit);
-    d.q_tiles = (d.Nq + q_per_run - 1) / q_per_run;
-    const int64_t runs = (int64_t)d.B * d.q_tiles * n_slices * d.H;
-    if (runs > 0x7fffffffLL) return hipErrorInvalidValue;
-    const int grid = (int)persistent_grid(runs, d.H);
-    hipLaunchKernelGGL((msda_fwd_q8<T>), dim3((unsigned)grid), dim3(kMmaThreads), lds_total, st,
-                       (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, q_per_run,
-                       lds_total, (int)runs, n_slices);
-    return hipGetLastError();
+    return launch_runs(d, q_per_run, n_slices, [&](const Dims &dq, dim3 grid, int runs) {
+        hipLaunchKernelGGL((msda_fwd_q8<T>), grid, dim3(kMmaThreads), lds_total, st,
+                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, dq, q_per_run,
+                           lds_total, runs, n_slices);
+    });
 }
 
 bool fwd_q8_supported(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return false;
-    if (d.D <= 0 || d.D % q8::kCS) return false;
-    if (d.L > kMmaMaxLevels || d.K <= 0 || d.K > q8::kMaxK || d.P <= 0) return false;
-    if ((int64_t)d.Nq * d.H * d.K >= (1LL << 30)) return false;            // 32-bit sample offsets inside a (b, h) slab
-    return (int64_t)d.S * d.H * d.D * 2 <= kMaxSlabBytes;
+    if (d.D <= 0 || d.D % q8::kCS || d.K > q8::kMaxK || d.P <= 0) return false;
+    return resident_shape_supported(dtype, d);
 }
 
 bool fwd_q8_applies(int dtype, const Dims &d)
@@ -651,8 +588,7 @@ bool fwd_q8_applies(int dtype, const Dims &d)
 hipError_t forward_q8(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
                       const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
 {
-    if (dtype == 1) return launch_q8<half_t>(value, shapes, start, loc, attn, out, d, st);
-    return launch_q8<bf16_t>(value, shapes, start, loc, attn, out, d, st);
+    return by_half_type(dtype, [&](auto t) { return launch_q8<decltype(t)>(value, shapes, start, loc, attn, out, d, st); });
 }
 
 }  // namespace mmfs
@@ -670,16 +606,7 @@ extern "C" int mmfs_debug_q8_probe(unsigned int *out, unsigned int *n, int reset
 #ifdef MMFS_PROFILE_Q8
 extern "C" int mmfs_debug_q8_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[mmfs::kQProfSlots * 8];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(mmfs::g_q8_prof), sizeof(host));
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    for (int s = 0; s < mmfs::kQProfSlots; ++s)
-        for (int i = 0; i < 8; ++i) out[i] += host[s * 8 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_q8_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N>(HIP_SYMBOL(mmfs::g_q8_prof), out, reset);
 }
 #endif
 

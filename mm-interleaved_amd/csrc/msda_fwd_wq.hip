@@ -45,25 +45,20 @@
 #include "msda_launch.h"
 #include <cstdlib>
 #include <type_traits>
+#ifdef MMFS_PROFILE_WQ
+#define MMFS_PROF_COUNTERS g_wq_prof
+#endif
+#define MMFS_PROF_SLOTS 4096
+#define MMFS_PROF_N 8
+#define MMFS_PROF_LANE ((threadIdx.x & 63) == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 
 using namespace mma;
 
 // Development aid (tools/exp_build.sh wqprof "-DMMFS_PROFILE_WQ"; tools/wq_prof.py): shader clocks per phase of a wave
-#ifdef MMFS_PROFILE_WQ
-constexpr int kWProfSlots = 4096;
-__device__ unsigned long long g_wq_prof[kWProfSlots * 8];
-#define WPROF_DECL unsigned long long wprof_c = __builtin_readcyclecounter(), wprof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define WPROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); wprof_t[i] += tn - wprof_c; wprof_c = tn; } while (0)
-#define WPROF_COUNT(i, v) do { wprof_t[i] += (unsigned long long)(v); } while (0)
-#define WPROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_wq_prof[(blockIdx.x % kWProfSlots) * 8 + i_], wprof_t[i_]); } while (0)
-#else
-#define WPROF_DECL do {} while (0)
-#define WPROF(i) do {} while (0)
-#define WPROF_COUNT(i, v) do {} while (0)
-#define WPROF_FLUSH() do {} while (0)
-#endif
+MMFS_PROF_STORAGE;
 
 namespace wq {
 
@@ -82,40 +77,23 @@ template <int D> struct Geom {
     static constexpr int IMG0 = (TAB_BYTES + kMmaWaves * kWaveRec + 255) & ~255;
 };
 
-// Level table -> LDS and which levels live in the image (smallest first, ties by index, while they fit behind the row
-// of zeros) -- msda_mma_common.h's rule at this kernel's pitch: a level is a linear run of Hl * Wl rows of RB bytes.
-template <int RB>
-__device__ __forceinline__ void build_table(int *tab, unsigned char *img, const int64_t *__restrict__ shapes,
-                                            const int64_t *__restrict__ start, int L, int tid, int img_budget)
-{
-    for (int l = tid; l < L; l += kMmaThreads) {
-        const int Hl = (int)shapes[2 * l], Wl = (int)shapes[2 * l + 1];
-        tab[kTabInts * l] = Hl; tab[kTabInts * l + 1] = Wl; tab[kTabInts * l + 2] = (int)start[l];
-        int bytes = (Hl > 0 && Wl > 0) ? 1 << 24 : 0;                     // "never fits"; an empty level takes no room
-        if (Hl > 0 && Wl > 0 && Hl <= 1024 && Wl <= 1024) {
-            const int64_t bb = ((int64_t)Hl * Wl * RB + 1023) & ~1023LL;  // (whole 1 KiB blocks: what a wave's DMA request fills)
-            if (bb < (1 << 24)) bytes = (int)bb;
-        }
-        tab[kTabInts * l + 4] = Wl * RB; tab[kTabInts * l + 5] = bytes;
+// The image (placement: build_level_table, msda_mma_common.h): a level is a linear run of Hl * Wl rows of RB bytes in
+// whole 1 KiB blocks (what a wave's DMA request fills), behind 1 KiB whose first row is the row of zeros.
+template <int RB> struct Image {
+    static constexpr int kStride = kTabInts, kMaxSide = 1024, kFirst = 1024;
+    static constexpr bool kZeroEarly = false;
+    static constexpr int kBorderLines = 0, kUnitBytes = RB, kBlock = 1024;
+    static constexpr bool kPaddedLines = false, kSlot4InBytes = true;
+    static __device__ __forceinline__ void zero(unsigned char *img, int tid, int)
+    {
+        if (tid < RB / 4) reinterpret_cast<uint32_t *>(img)[tid] = 0u;
     }
-    __syncthreads();
-    for (int l = tid; l < L; l += kMmaThreads) {
-        const int px = tab[kTabInts * l] * tab[kTabInts * l + 1], bytes = tab[kTabInts * l + 5];
-        int cum = 0;
-        for (int l2 = 0; l2 < L; ++l2) {
-            const int px2 = tab[kTabInts * l2] * tab[kTabInts * l2 + 1];
-            if (px2 < px || (px2 == px && l2 <= l)) cum += tab[kTabInts * l2 + 5];
-        }
-        tab[kTabInts * l + 3] = (cum + 1024 <= img_budget && px > 0) ? 1024 + cum - bytes : -1;     // (the row of zeros comes first)
-    }
-    if (tid < RB / 4) reinterpret_cast<uint32_t *>(img)[tid] = 0u;
-    __syncthreads();
-}
+};
 
 // Resident levels global -> LDS, once per run of queries: a linear copy by DMA (buffer_load ... lds: 64 pieces of 16 bytes
 // per wave request land in 1 KiB of consecutive LDS, no registers in between), every request of every level issued before
 // the one wait (fill_wait: the caller stages its first samples in between) -- one round trip per run, not one per level.  A level's room in the image is a whole number of
-// 1 KiB blocks (build_table), so the lanes past the end of its last block write into padding.
+// 1 KiB blocks (wq::Image), so the lanes past the end of its last block write into padding.
 template <int RB>
 __device__ __forceinline__ void fill_image(const int *tab, uint32_t img_lds, const u32x4 rsrc_words,
                                            uint32_t row_bytes, int L, int S, int wave, int lane)
@@ -179,11 +157,11 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    WPROF_DECL;
+    PROF_DECL;
     const int L = d.L;
     const int64_t HD = (int64_t)d.H * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
-    wq::build_table<G::RB>(tab, img, shapes, start, L, tid, img_budget);
+    build_level_table<wq::Image<G::RB>>(tab, img, shapes, start, L, tid, img_budget);
 
     // ---- lane roles
     const int cj = lane >> 4;                                             // corner whose row this lane loads / whose weight it holds
@@ -247,7 +225,7 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
     };
     prefetch(0);
     if (run != (int)blockIdx.x) __syncthreads();                          // every wave is done with the previous image
-    WPROF(0);
+    PROF(0);
     // (the first group's sample words are waited for HERE -- they were requested before the barrier -- so that its staging,
     //  which runs while the image is on its way, meets no memory wait of its own)
     asm volatile("" : "+v"(pf_w0), "+v"(pf_w1), "+v"(pf_a));
@@ -360,13 +338,13 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
             wave_sync();
         }
         if (step == 0) {
-            WPROF(1);
+            PROF(1);
             wq::fill_wait();
-            WPROF(4);
+            PROF(4);
         }
         prefetch(step + 1);
         __builtin_amdgcn_sched_barrier(0);
-        WPROF(1);
+        PROF(1);
 
         // ---- the group's queries, one after the other: every sample one product
         auto lds_u4 = [](uint32_t addr) -> uint4 {
@@ -492,7 +470,7 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
                     if (!finish(acc[0], q0 + qi)) redo |= 1u << qi;
                 }
             }
-            WPROF(2);
+            PROF(2);
         } else {
             // (a rolled loop over the queries: the accumulator of query qi moves through a4 by wave-uniform selects)
 #pragma unroll 1
@@ -506,7 +484,7 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
 #pragma unroll
                 for (int j = 0; j < (MULTI ? QG : 1); ++j) acc[j] = qi == j ? a4 : acc[j];
             }
-            WPROF(2);
+            PROF(2);
         }
         // (the next step's sample words have arrived long since: waiting for them HERE leaves the top of the loop without a
         //  pending request of the compiler's own, so that the staging of a run's first group does not wait for the image)
@@ -521,9 +499,9 @@ msda_fwd_wq(const T *__restrict__ value, const int64_t *__restrict__ shapes,
             wq::exact_query<T, D>(tab, rsrc, row_bytes, lq, aq, d.K, d.P, out + (((int64_t)b * d.Nq + q) * d.H + h) * d.D, lane);
         }
     }
-    WPROF_COUNT(7, n_steps);
+    PROF_COUNT(7, n_steps);
     }   // runs
-    WPROF_FLUSH();
+    PROF_FLUSH();
 }
 
 // ---------------------------------------------------------------- launcher
@@ -532,39 +510,22 @@ static hipError_t launch_wq(const void *value, const int64_t *shapes, const int6
                             const void *loc, const void *attn, void *out, Dims d, hipStream_t st)
 {
     typedef wq::Geom<D> G;
-    static const hipError_t once1 = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_wq<T, D, false>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
-    static const hipError_t once2 = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_wq<T, D, true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
-    if (once1 != hipSuccess) return once1;
-    if (once2 != hipSuccess) return once2;
-    const int env_kb = knob_int(K_FWD_WQ_LDS_KB, 0);       // tuning / tests
-    const int lds_total = env_kb > 0 ? std::min(kLdsTotal, std::max(G::IMG0 + 1024, env_kb * 1024)) : kLdsTotal;
-    const int env_q = knob_int(K_FWD_WQ_QPW, 0);
-    const int unit = kMmaWaves * wq::kGroup;
-    const int q_per_wg = pick_queries_per_run(d, unit, env_q);       // (256, or shorter runs for few queries: msda_mma_common.h)
-    d.q_tiles = (d.Nq + q_per_wg - 1) / q_per_wg;
-    const int64_t runs = (int64_t)d.B * d.q_tiles * d.H;
-    if (runs > 0x7fffffffLL) return hipErrorInvalidValue;
-    const int grid = (int)persistent_grid(runs, d.H);
-    if (d.K <= kChunk)
-        hipLaunchKernelGGL((msda_fwd_wq<T, D, false>), dim3((unsigned)grid), dim3(kMmaThreads), lds_total, st,
-                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, q_per_wg,
-                           lds_total - G::IMG0, (int)runs);
-    else
-        hipLaunchKernelGGL((msda_fwd_wq<T, D, true>), dim3((unsigned)grid), dim3(kMmaThreads), lds_total, st,
-                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, d, q_per_wg,
-                           lds_total - G::IMG0, (int)runs);
-    return hipGetLastError();
+    if (const hipError_t e = allow_full_lds<&msda_fwd_wq<T, D, false>>()) return e;
+    if (const hipError_t e = allow_full_lds<&msda_fwd_wq<T, D, true>>()) return e;
+    const int lds_total = lds_bytes(K_FWD_WQ_LDS_KB, G::IMG0);
+    const int q_per_wg = pick_queries_per_run(d, kMmaWaves * wq::kGroup, knob_int(K_FWD_WQ_QPW, 0));    // (256, or shorter runs for few queries: msda_mma_common.h)
+    return launch_runs(d, q_per_wg, 1, [&](const Dims &dq, dim3 grid, int runs) {
+        // (one chunk of samples per query: the straight-line kernel)
+        const auto kernel = d.K <= kChunk ? &msda_fwd_wq<T, D, false> : &msda_fwd_wq<T, D, true>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kMmaThreads), lds_total, st,
+                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (T *)out, dq, q_per_wg,
+                           lds_total - G::IMG0, runs);
+    });
 }
 
 bool fwd_wq_supported(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return false;
-    if (d.D != 128) return false;
-    if (d.L > kMmaMaxLevels || d.K <= 0) return false;
-    if ((int64_t)d.Nq * d.H * d.K >= (1LL << 30)) return false;            // 32-bit sample offsets inside a (b, h) slab
-    return (int64_t)d.S * d.H * d.D * 2 <= kMaxSlabBytes;
+    return d.D == 128 && resident_shape_supported(dtype, d);
 }
 
 bool fwd_wq_applies(int dtype, const Dims &d)
@@ -583,8 +544,7 @@ bool fwd_wq_applies(int dtype, const Dims &d)
 hipError_t forward_wq(int dtype, const void *value, const int64_t *shapes, const int64_t *start,
                       const void *loc, const void *attn, void *out, const Dims &d, hipStream_t st)
 {
-    if (dtype == 1) return launch_wq<half_t, 128>(value, shapes, start, loc, attn, out, d, st);
-    return launch_wq<bf16_t, 128>(value, shapes, start, loc, attn, out, d, st);
+    return by_half_type(dtype, [&](auto t) { return launch_wq<decltype(t), 128>(value, shapes, start, loc, attn, out, d, st); });
 }
 
 }  // namespace mmfs
@@ -592,15 +552,6 @@ hipError_t forward_wq(int dtype, const void *value, const int64_t *shapes, const
 #ifdef MMFS_PROFILE_WQ
 extern "C" int mmfs_debug_wq_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[mmfs::kWProfSlots * 8];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(mmfs::g_wq_prof), sizeof(host));
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    for (int s = 0; s < mmfs::kWProfSlots; ++s)
-        for (int i = 0; i < 8; ++i) out[i] += host[s * 8 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_wq_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N>(HIP_SYMBOL(mmfs::g_wq_prof), out, reset);
 }
 #endif

@@ -30,25 +30,20 @@
 #include <cstring>
 #include "msda_launch.h"
 #include <cstdlib>
+#ifdef MMFS_PROFILE_TAPS
+#define MMFS_PROF_COUNTERS g_taps_prof
+#endif
+#define MMFS_PROF_SLOTS 4096
+#define MMFS_PROF_N 8
+#define MMFS_PROF_LANE ((threadIdx.x & 63) == 0)
+#include "msda_prof.h"
 
 namespace mmfs {
 
 using namespace mma;
 
 // Development aid (tools/exp_build.sh tapsprof "-DMMFS_PROFILE_TAPS"; tools/taps_prof.py): shader clocks per phase of a wave
-#ifdef MMFS_PROFILE_TAPS
-constexpr int kTProfSlots = 4096;
-__device__ unsigned long long g_taps_prof[kTProfSlots * 8];
-#define APROF_DECL unsigned long long aprof_c = __builtin_readcyclecounter(), aprof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define APROF(i) do { const unsigned long long tn = __builtin_readcyclecounter(); aprof_t[i] += tn - aprof_c; aprof_c = tn; } while (0)
-#define APROF_COUNT(i, v) do { aprof_t[i] += (unsigned long long)(v); } while (0)
-#define APROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_taps_prof[(blockIdx.x % kTProfSlots) * 8 + i_], aprof_t[i_]); } while (0)
-#else
-#define APROF_DECL do {} while (0)
-#define APROF(i) do {} while (0)
-#define APROF_COUNT(i, v) do {} while (0)
-#define APROF_FLUSH() do {} while (0)
-#endif
+MMFS_PROF_STORAGE;
 
 #ifndef MMFS_TAPS_CHAINS
 #define MMFS_TAPS_CHAINS 1      // measured (r03h): 1: 144.7 us, 2: 152.4 us (the second chain's registers spill)
@@ -79,8 +74,8 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
     const int L = d.L;
     const int64_t HD = (int64_t)d.H * d.D;
     const uint32_t row_bytes = (uint32_t)(HD * sizeof(T));
-    APROF_DECL;
-    build_level_table<D>(tab, img, shapes, start, L, tid, img_budget);
+    PROF_DECL;
+    build_level_table<PitchedImage<D, false>>(tab, img, shapes, start, L, tid, img_budget);
     // one run per workgroup, or persistent workgroups (persistent_grid, msda_mma_common.h)
     for (int run = blockIdx.x; run < n_runs; run += gridDim.x) {
     const int h = run % d.H;
@@ -133,9 +128,9 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
     prefetch(0);
     // ---- the run's image
     if (run != (int)blockIdx.x) __syncthreads();                          // every wave is done with the previous image
-    APROF(0);                                                             // run setup + barrier
-    fill_image<D, false>(tab, img, rsrc, row_bytes, L, d.S, tid);         // natural channel order
-    APROF(1);                                                             // image fill
+    PROF(0);                                                             // run setup + barrier
+    fill_image<PitchedImage<D, false>>(tab, img, rsrc, row_bytes, L, d.S, tid);         // natural channel order
+    PROF(1);                                                             // image fill
     uint4 graw = make_uint4(0u, 0u, 0u, 0u);                              // this lane's 16 bytes of its query's grad_out row
     s16x8 Bf[NKS];                                                        // B operand: the wave's queries, all of D
 
@@ -228,7 +223,7 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
             if (k_ok) *reinterpret_cast<uint4 *>(wrec + (ps * 4 + (lane >> 4)) * G::QSTRIDE + ridx * 32) = r0;
         }
         wave_sync();
-        APROF(2);                                                         // stage
+        PROF(2);                                                         // stage
         if (chunk == 0) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
@@ -302,10 +297,10 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
                 issue(r0, g0); issue(r1, g1); issue(r2, g2); issue(r3, g3);
                 prefetch(step + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                APROF(3);                                                 // first issues + next requests
+                PROF(3);                                                 // first issues + next requests
                 mma_phase();
                 __builtin_amdgcn_sched_barrier(0);
-                APROF(4);                                                 // matrix-core phase
+                PROF(4);                                                 // matrix-core phase
                 for (int i = 4; i < n_live; i += 4) {
                     consume(r0, g0); issue(r0, g0);
                     consume(r1, g1); issue(r1, g1);
@@ -313,7 +308,7 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
                     consume(r3, g3); issue(r3, g3);
                 }
                 consume(r0, g0); consume(r1, g1); consume(r2, g2); consume(r3, g3);
-                APROF(5);                                                 // gather loop
+                PROF(5);                                                 // gather loop
             } else {
                 prefetch(step + 1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -358,11 +353,11 @@ msda_taps_mma(const T *__restrict__ value, const int64_t *__restrict__ shapes, c
                 store_xy(gl_wg, (int64_t)s, pair_ok, (float)Wl * dw * a, (float)Hl * dh * a);
             }
         }
-        APROF(6);                                                         // per-sample algebra + stores
+        PROF(6);                                                         // per-sample algebra + stores
     }
-    APROF_COUNT(7, n_steps);
+    PROF_COUNT(7, n_steps);
     }   // runs
-    APROF_FLUSH();
+    PROF_FLUSH();
     // ---- the opening launch of the grad_value half, hosted here (one launch less per backward): the FIRST workgroup
     // clears the sort's cursors and plans it; its LDS is free by now.  (One workgroup per run: it is done long before the
     // kernel is.  Persistent workgroups all end together and the plan is 4 us of one of them: a workgroup of its own
@@ -383,29 +378,19 @@ static hipError_t launch_taps_mma(const void *value, const int64_t *shapes, cons
     if (job != nullptr) jb = *job;
     else { memset(&jb, 0, sizeof(jb)); }
     typedef MmaGeom<D, (64 / (D * 2 / 16)) * D * 2> G;
-    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_taps_mma<T, D>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
-    if (once != hipSuccess) return once;
-    const int env_q = knob_int(K_TAPS_MMA_QPW, 0);
-    const int unit = kMmaWaves * G::QPW;
-    const int q_per_wg = pick_queries_per_run(d, unit, env_q);       // (256, or shorter runs for few queries: msda_mma_common.h)
-    d.q_tiles = (d.Nq + q_per_wg - 1) / q_per_wg;
-    const int64_t runs = (int64_t)d.B * d.q_tiles * d.H;
-    if (runs > 0x7fffffffLL) return hipErrorInvalidValue;
-    const int grid = (int)persistent_grid(runs, d.H);                       // (one workgroup per CU when there are many runs, else = runs)
-    hipLaunchKernelGGL((msda_taps_mma<T, D>), dim3((unsigned)grid), dim3(kMmaThreads), kLdsTotal, st,
-                       (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (const T *)go, (T *)gl, (T *)ga,
-                       d, q_per_wg, kLdsTotal - G::IMG0, (int)runs, jb);
-    return hipGetLastError();
+    if (const hipError_t e = allow_full_lds<&msda_taps_mma<T, D>>()) return e;
+    const int q_per_wg = pick_queries_per_run(d, kMmaWaves * G::QPW, knob_int(K_TAPS_MMA_QPW, 0));  // (256, or shorter runs for few queries: msda_mma_common.h)
+    // (no LDS knob: always the whole CU's)
+    return launch_runs(d, q_per_wg, 1, [&](const Dims &dq, dim3 grid, int runs) {
+        hipLaunchKernelGGL((msda_taps_mma<T, D>), grid, dim3(kMmaThreads), kLdsTotal, st,
+                           (const T *)value, shapes, start, (const T *)loc, (const T *)attn, (const T *)go, (T *)gl, (T *)ga,
+                           dq, q_per_wg, kLdsTotal - G::IMG0, runs, jb);
+    });
 }
 
 bool taps_mma_supported(int dtype, const Dims &d)
 {
-    if (dtype != 1 && dtype != 2) return false;
-    if (d.D != 128 && d.D != 64) return false;
-    if (d.L > kMmaMaxLevels || d.K <= 0) return false;
-    if ((int64_t)d.Nq * d.H * d.K >= (1LL << 30)) return false;            // 32-bit sample offsets inside a (b, h) slab
-    return (int64_t)d.S * d.H * d.D * 2 <= kMaxSlabBytes;
+    return (d.D == 128 || d.D == 64) && resident_shape_supported(dtype, d);
 }
 
 bool taps_mma_applies(int dtype, const Dims &d)
@@ -422,12 +407,11 @@ hipError_t backward_taps_mma(int dtype, const void *value, const int64_t *shapes
                              const void *loc, const void *attn, const void *grad_out, void *grad_loc, void *grad_attn,
                              const Dims &d, hipStream_t st, const blk::PrepareJob *job)
 {
-    if (d.D == 64) {
-        if (dtype == 1) return launch_taps_mma<half_t, 64>(value, shapes, start, loc, attn, grad_out, grad_loc, grad_attn, d, st, job);
-        return launch_taps_mma<bf16_t, 64>(value, shapes, start, loc, attn, grad_out, grad_loc, grad_attn, d, st, job);
-    }
-    if (dtype == 1) return launch_taps_mma<half_t, 128>(value, shapes, start, loc, attn, grad_out, grad_loc, grad_attn, d, st, job);
-    return launch_taps_mma<bf16_t, 128>(value, shapes, start, loc, attn, grad_out, grad_loc, grad_attn, d, st, job);
+    return by_int<64, 128>(d.D, [&](auto w) {
+        return by_half_type(dtype, [&](auto t) {
+            return launch_taps_mma<decltype(t), decltype(w)::value>(value, shapes, start, loc, attn, grad_out, grad_loc, grad_attn, d, st, job);
+        });
+    });
 }
 
 }  // namespace mmfs
@@ -435,15 +419,6 @@ hipError_t backward_taps_mma(int dtype, const void *value, const int64_t *shapes
 #ifdef MMFS_PROFILE_TAPS
 extern "C" int mmfs_debug_taps_profile(unsigned long long *out, int reset)
 {
-    static unsigned long long host[mmfs::kTProfSlots * 8];
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(mmfs::g_taps_prof), sizeof(host));
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    for (int s = 0; s < mmfs::kTProfSlots; ++s)
-        for (int i = 0; i < 8; ++i) out[i] += host[s * 8 + i];
-    if (e == hipSuccess && reset) {
-        for (auto &v : host) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(mmfs::g_taps_prof), host, sizeof(host));
-    }
-    return (int)e;
+    return mmfs::prof_readout<MMFS_PROF_SLOTS, MMFS_PROF_N>(HIP_SYMBOL(mmfs::g_taps_prof), out, reset);
 }
 #endif

@@ -39,14 +39,14 @@ from helpers import OUTPUTS, bound_ratios, error_bounds, level_tables, make_inpu
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-# The query-wave forward's image budget at D = 128 (csrc/msda_fwd_wq.hip, launch_wq / build_table):
+# The query-wave forward's image budget at D = 128 (csrc/msda_fwd_wq.hip, launch_wq / wq::Image):
 #   table   TAB_BYTES = round_up(kMmaMaxLevels 64 * kTabInts 6 * 4 + 64, 256)            =   1 792 bytes
 #   waves   kMmaWaves 16 * kWaveRec (kGroup 4 * kQStride (4 batches * 208 bytes))          =  53 248
 #   IMG0    round_up(1 792 + 53 248, 256) = 55 040;  budget = kLdsTotal 160 KiB - IMG0   = 108 800
 # A level takes ceil(H * W * 256 bytes / 1 KiB) KiB and is resident (smallest first) while the running sum + the 1 KiB
 # row of zeros <= 108 800, i.e. while the sum <= 105 KiB.  (4, 41) = 164 px = 41 KiB, then (16, 16) = 64 KiB: 105 KiB,
 # both resident, the budget's last whole KiB used.  (17, 16) = 68 KiB: 109 KiB, the larger level goes to the row gather.
-# (The sliced and matrix-core kernels' budgets are not derived here: their tables run at D = 32 / 64 all the same.)
+# The other three LDS-resident kernels' budgets: BUDGET_TABLES below, computed from their formulas.
 TABLES = [
     # name                 shapes
     ("empty_first_0xW",    [(0, 7), (8, 8), (4, 4)]),
@@ -71,7 +71,71 @@ TABLES = [
     ("row_1025px",         [(1, 1025), (2, 2)]),
     ("wq_budget_exact",    [(16, 16), (0, 3), (4, 41)]),
     ("wq_budget_over",     [(17, 16), (0, 3), (4, 41)]),
+    # two levels of equal pixel count around an empty one: the lower index is placed first, the empty level takes no room
+    # and is never resident.  Both fit every image; of the second pair one level alone fits the images at D = 128 (query
+    # waves: 80 KiB each of 105; matrix cores: 95 232 and 93 440 bytes of 127 968 / 111 584)
+    ("equal_px_both_fit",  [(6, 10), (0, 3), (10, 6)]),
+    ("equal_px_one_fits",  [(16, 20), (0, 3), (20, 16)]),
 ]
+
+
+# ---- the exact-budget boundary of the other LDS-resident kernels, from their own formulas (csrc/msda_mma_common.h,
+# csrc/msda_fwd_q8.hip, csrc/msda_taps_mma.hip); kLdsTotal = 160 KiB, 16 waves, level table of 64 levels.
+def _round_up(x, m):
+    return (x + m - 1) // m * m
+
+
+def _mma_image(D, extra):
+    """(bytes of a level, largest admissible sum of the resident levels' bytes) of the matrix-core image at head width D:
+    pixel rows RP = 2 D + 32 bytes apart, lines at line_pitch; wave-private bytes = the sample records (QPW queries x 33 x
+    16 bytes) + ``extra``; a level is placed while sum + RP (the zero row) <= kLdsTotal - IMG0."""
+    RP, QPW = 2 * D + 32, 64 // (2 * D // 16)
+    img0 = _round_up(_round_up(64 * 6 * 4 + 64, 256) + 16 * (QPW * 33 * 16 + extra), 256)
+    pitch = lambda W: W * RP + ((64 - W * RP % 256) & 255)
+    return (lambda Hl, Wl: Hl * pitch(Wl)), 160 * 1024 - img0 - RP
+
+
+def _q8_image():
+    """The sliced forward's: Hl + 2 lines of line_pixels(Wl) pixels of 64 bytes; placed while kImg0 + sum <= kLdsTotal,
+    kImg0 = round_up(table 64 * 8 * 4 + per-sample table 128 * 32 + 16 waves * 3072, 256)."""
+    img0 = _round_up(64 * 8 * 4 + 128 * 32 + 16 * 3072, 256)
+    line_pixels = lambda W: W + 2 + ((4 - (W & 3)) & 3)
+    return (lambda Hl, Wl: (Hl + 2) * line_pixels(Wl) * 64), 160 * 1024 - img0
+
+
+def _budget_pair(level_bytes, limit):
+    """Two levels, the second with more pixels, whose bytes end as close under ``limit`` as two levels of this image can
+    (exactly on it where the formula's granularity allows: asserted per kernel below), and the same pair with one more
+    line of the larger level: over the limit.  -> (shapes that fit, shapes one line over, bytes left under the limit)"""
+    best = None
+    for h1 in (3, 4, 5):
+        for w1 in range(3, 13):
+            for w2 in range(13, 73):
+                per_line = level_bytes(2, w2) - level_bytes(1, w2)                # (bytes are affine in the lines)
+                h2 = 1 + (limit - level_bytes(h1, w1) - level_bytes(1, w2)) // per_line
+                if not 13 <= h2 <= 72:
+                    continue
+                left = limit - level_bytes(h1, w1) - level_bytes(h2, w2)
+                if best is None or left < best[0]:
+                    best = (left, [(h2, w2), (0, 3), (h1, w1)], [(h2 + 1, w2), (0, 3), (h1, w1)])
+    left, fits, over = best
+    assert left >= 0 and limit - sum(level_bytes(h, w) for h, w in over if h * w) < 0
+    return fits, over, left
+
+
+# kernel (forced by fwd="lds" / "slices", taps="lds"), head width -> its image.  msda_taps_mma keeps the wave's grad_out
+# rows (QPW * 2 D = 1024 bytes) besides the records.
+_IMAGES = {"mma128": (128, _mma_image(128, 0)), "mma64": (64, _mma_image(64, 0)),
+           "taps128": (128, _mma_image(128, 1024)), "taps64": (64, _mma_image(64, 1024)), "q8": (64, _q8_image())}
+BUDGET_TABLES, BUDGET_D = [], {}
+for _k, (_D, (_bytes, _limit)) in _IMAGES.items():
+    _fits, _over, _left = _budget_pair(_bytes, _limit)
+    # the matrix-core image's levels are multiples of 64 bytes and its limit is 32 short of one: 32 bytes stay free on the
+    # last admissible sum; the sliced image's limit is met to the byte
+    assert _left == (0 if _k == "q8" else 32), (_k, _left)
+    BUDGET_TABLES += [(f"{_k}_budget_exact", _fits), (f"{_k}_budget_over", _over)]
+    BUDGET_D.update({f"{_k}_budget_exact": _D, f"{_k}_budget_over": _D})
+TABLES += BUDGET_TABLES
 NAMES = [n for n, _ in TABLES]
 SHAPES = dict(TABLES)
 B, H, NQ, P = 1, 2, 48, 4
@@ -98,9 +162,12 @@ def has_empty(shapes):
     return any(h * w == 0 for h, w in shapes)
 
 
-def head_widths(shapes):
+def head_widths(shapes, name=None):
     """D = 128 for the query-wave kernel, 64 and 32 for the sliced / matrix-core ones, 24 and 8 for the scalar gather;
-    only 32 on the tables of tens of thousands of pixels (the bound's arrays are S * H * D doubles)."""
+    only 32 on the tables of tens of thousands of pixels (the bound's arrays are S * H * D doubles); a budget table of
+    BUDGET_TABLES at the head width its sizes were computed for."""
+    if name in BUDGET_D:
+        return (BUDGET_D[name],)
     return (32,) if sum(h * w for h, w in shapes) > 30000 else (128, 64, 32, 24, 8)
 
 
@@ -201,7 +268,7 @@ def _run_table(name):
     import MultiScaleDeformableAttention as MSDA
     shapes = SHAPES[name]
     fails, fwd_ran, bwd_ran = [], {}, {}
-    for D in head_widths(shapes):
+    for D in head_widths(shapes, name):
         for dtype in dtypes_of(name, shapes):
             if dtype == torch.float64 and D != 32:
                 continue
