@@ -1,5 +1,6 @@
 // mmfs_attn_core.h -- what the attention kernels share (mmfs_attn.hip: the Q-Former, D = 64; mmfs_llama_attn.hip: decode,
-// mmfs_llama_prefill.hip: prefill, mmfs_llama_train.hip: training, D = 128; mmfs_text_loss.hip takes exp_hw alone): exp by the hardware's exp2, finfo(T).min
+// mmfs_llama_prefill.hip: prefill, mmfs_llama_train.hip: training, D = 128; mmfs_clip_attn.hip: the CLIP ViT, D = 64;
+// mmfs_text_loss.hip takes exp_hw alone): exp by the hardware's exp2, finfo(T).min
 // and the masked-key rule, the fragment helpers of the 16x16x32 matrix products, and on the host side the checks that the
 // LLaMA entries make alike.  The online-softmax tile step of qk_attn_fwd and llama_attn_prefill is NOT here: each kernel
 // keeps its loop (profiles/attn_core.md says what a shared routine measured).
@@ -111,13 +112,29 @@ inline int llama_train_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t
     return llama_train_supported(dtype, D, L ? L : 1) ? MMFS_OK : MMFS_E_UNSUPPORTED;
 }
 
-// their bias argument: -> status and the type flag (fp32 without a bias); the strides are the entry's own to judge
+// the LLaMA entries' bias argument: -> status and the type flag (fp32 without a bias); the strides are the entry's own to judge
 inline int llama_bias(const void *bias, int bias_dtype, int dtype, int64_t bias_len, int &bias_f32)
 {
     bias_f32 = bias ? small_f32(bias_dtype, dtype) : 1;
     if (bias_f32 < 0) return MMFS_E_DTYPE;
     if (bias && (bias_len < 0 || bias_len > kLlamaMaxCap)) return MMFS_E_DIMS;
     return MMFS_OK;
+}
+
+// the CLIP ViT entries (mmfs_clip_attn.hip): plain self-attention, heads of 64 channels, L tokens a row; an empty problem
+// (B, H or L of 0) is no error
+constexpr int kClipD = 64;
+constexpr int64_t kClipMaxL = 1 << 22;
+
+inline bool clip_supported(int dtype, int64_t D, int64_t L)
+{
+    return (dtype == MMFS_F16 || dtype == MMFS_BF16) && D == kClipD && L >= 1 && L <= kClipMaxL;
+}
+
+inline int clip_check(int dtype, int64_t B, int64_t H, int64_t D, int64_t L)
+{
+    if (const int rc = batch_heads_check(dtype, B, H, D, L, 0)) return rc;
+    return clip_supported(dtype, D, L ? L : 1) ? MMFS_OK : MMFS_E_UNSUPPORTED;
 }
 
 }  // namespace attn

@@ -2,6 +2,8 @@
 include/mmfs_msda.h in the header's order, and ``bind``, which applies it to a ``ctypes.CDLL`` handle.  The shim
 (MultiScaleDeformableAttention.py, next to this file) binds the library once; the tests bind their own handle with the
 same call.  tests/test_capi.py parses the header and holds this table to it, name by name and argument by argument.
+Entries added beside that header keep a table of their own (``CLIP_ATTN_SIGNATURES``: include/mmfs_clip_attn.h), which
+``bind`` applies as well.
 """
 import ctypes
 import re
@@ -99,14 +101,31 @@ mmfs_env_reload                                 v
 mmfs_env_knob                                   i  i p3
 """
 
+# include/mmfs_clip_attn.h, in its order: additive entries that live in a header of their own (the ABI version does not move;
+# tests/test_clip_attn.py holds this table to that header)
+_CLIP_ATTN_TABLE = """
+mmfs_clip_attn_supported                        i  i ll
+mmfs_clip_attn_tiles                            l  i
+mmfs_clip_attn_workspace_bytes                  l  l3
+mmfs_clip_attn_forward                          i  i p5 l4 p
+mmfs_clip_attn_backward                         i  i p10 l5 p
+"""
+
 _KIND = {"i": ctypes.c_int, "l": ctypes.c_int64, "u": ctypes.c_uint, "f": ctypes.c_float, "p": ctypes.c_void_p,
          "s": ctypes.c_char_p, "v": None}
 
+
+def _parse(table):
+    out = {}
+    for line in table.strip().splitlines():
+        name, ret, *args = line.split()
+        out[name] = (ret, re.sub(r"(.)(\d+)", lambda m: m[1] * int(m[2]), "".join(args)))
+    return out
+
+
 # {name: (return kind, argument kinds -- one letter per argument)}, in the header's order
-SIGNATURES = {}
-for _line in _TABLE.strip().splitlines():
-    _name, _ret, *_args = _line.split()
-    SIGNATURES[_name] = (_ret, re.sub(r"(.)(\d+)", lambda m: m[1] * int(m[2]), "".join(_args)))
+SIGNATURES = _parse(_TABLE)
+CLIP_ATTN_SIGNATURES = _parse(_CLIP_ATTN_TABLE)
 
 # the one entry point whose pointers are typed: it hands three strings back
 _TYPED = {"mmfs_env_knob": [ctypes.c_int] + [ctypes.POINTER(ctypes.c_char_p)] * 3}
@@ -118,9 +137,9 @@ FLOAT_CODE = {t: c for t, c in DTYPE_CODE.items() if t != torch.float64}
 
 
 def bind(lib):
-    """Give every entry point of the table its ``restype`` / ``argtypes`` on ``lib`` (a ``ctypes.CDLL``); -> ``lib``.
+    """Give every entry point of the two tables its ``restype`` / ``argtypes`` on ``lib`` (a ``ctypes.CDLL``); -> ``lib``.
     A name the library does not export raises ImportError."""
-    for name, (ret, args) in SIGNATURES.items():
+    for name, (ret, args) in {**SIGNATURES, **CLIP_ATTN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:

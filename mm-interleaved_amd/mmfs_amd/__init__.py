@@ -18,11 +18,15 @@ and the callers either side of the op:
                          a key / value cache written in place (re-indexed, not copied, under beam search), prompt and single-token
                          attention over it; in training, causal attention forward and backward with no L x L tensor
                          (``llama_attn_train``, the module's training route)
+    mmfs_amd.clip_attn   CLIPSelfAttention, convert_clip_visual_attn, clip_attention: the image encoder's (CLIP ViT) self-attention,
+                         heads of 64 channels, forward and backward with no L x L tensor
 """
 from .functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch  # noqa: F401
 from .functions import QKNormAttentionFunction, qk_attn_supported  # noqa: F401
 from .functions import llama_attn_decode, llama_attn_prefill, llama_attn_supported, llama_rope_append, rope_table  # noqa: F401
 from .functions import LlamaAttnTrainFunction, llama_attn_train, llama_attn_train_supported  # noqa: F401
+from .functions import ClipAttentionFunction, clip_attn_supported  # noqa: F401
+from .clip_attn import CLIPSelfAttention, clip_attention, convert_clip_visual_attn  # noqa: F401
 from .levels import invalidate_caches  # noqa: F401
 from .llama_attn import LlamaKVCache, LlamaKVLayer, LlamaSelfAttention  # noqa: F401
 from .resampler import QKNormAttention  # noqa: F401

@@ -10,3 +10,4 @@ from .sequence_func import ContextGatherFunction, SequenceEmbedFunction, sequenc
 from .qk_attn_func import QKNormAttentionFunction, qk_attn_supported  # noqa: F401,E402
 from .llama_attn_func import llama_attn_decode, llama_attn_prefill, llama_attn_supported, llama_rope_append, rope_table  # noqa: F401,E402
 from .llama_train_func import LlamaAttnTrainFunction, llama_attn_train, llama_attn_train_supported  # noqa: F401,E402
+from .clip_attn_func import ClipAttentionFunction, clip_attn_supported  # noqa: F401,E402
