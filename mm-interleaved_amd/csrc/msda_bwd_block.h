@@ -142,6 +142,27 @@ struct TileDesc {
 };
 static_assert(sizeof(TileDesc) == 64, "one 64-byte line per block");
 struct TileItem { uint32_t bh, blk, part, pidx; };          // one extra work item (part >= 1)
+// Two whole blocks (by, bx) and (by, bx + 1), bx even, of one level as ONE work item of 4 x 8 pixels (msda_bwd_tile.hip).
+// A block's run r is the records of cells 4 bx .. 4 bx + 4 of one cell row and a cell row's records are contiguous, so the
+// pair's run r is contiguous too -- cells 4 bx .. 4 bx + 8, the shared cell 4 bx + 4 once: it starts where t0's starts and
+// ends where t1's ends.  m: t0 with the five merged runs.  True when the two may be merged: both whole, same level and
+// block row, neighbours with the even one first, runs that do overlap in this way, and at most `chunk` records together.
+// A pure function of the two descriptors: the waves of both blocks evaluate it and decide alike.
+__host__ __device__ inline bool tile_pair(const TileDesc &t0, const TileDesc &t1, int chunk, TileDesc &m)
+{
+    m = t0;
+    if (t0.parts > 1u || t1.parts > 1u || t0.hw != t1.hw || t0.lstart != t1.lstart) return false;
+    if ((t0.byx & 1u) || t1.byx != t0.byx + 1u) return false;
+    long long n = 0;
+    bool ok = true;
+    for (int r = 0; r <= kTB; ++r) {
+        const long long c = (long long)t1.first[r] + t1.cnt[r] - t0.first[r];
+        ok = ok && c >= t0.cnt[r] && c >= t1.cnt[r] && c <= (long long)t0.cnt[r] + t1.cnt[r];
+        m.cnt[r] = (int)c;
+        n += c;
+    }
+    return ok && n <= chunk;
+}
 // grad_loc / grad_attn from the same cell-sorted records (msda_bwd_taps_sorted.hip): every cell -- every sample -- has ONE
 // owner block there: the block whose pixels hold the cell's own pixel (cy, cx) -> block (cy / 4, cx / 4), the last block
 // row / column also taking the border cells cy = Hl / cx = Wl.  The owned cells of a run are its first ones (a run is

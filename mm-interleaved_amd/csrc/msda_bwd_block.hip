@@ -1480,10 +1480,56 @@ hipError_t backward_value_block_reduce(int dtype, const void *grad_out, void *gr
 
 }  // namespace mmfs
 
+// tile_pair (msda_bwd_block.h) on one block row of a level Wl pixels wide: the runs of every block as the plan writes them
+// (a run = the cells 4 bx .. min(4 bx + 4, Wl) of a cell row, `first` = the records before it) from made-up cell counts,
+// every ordered couple of blocks (b0, b1).  Mergeable exactly when b0 is even, b1 = b0 + 1 and the merged list fits the
+// chunk -- for chunks one below, at and above the pair's length; the merged run is then the cells 4 b0 .. min(4 b0 + 8, Wl),
+// the shared cell once.  A cut partner, another block row and another level refuse.  -> what is wrong, counted.
+static int pair_selfcheck(int Wl, int nbx4)
+{
+    using namespace mmfs::blk;
+    const int Wc = Wl + 1;
+    std::vector<int> off((size_t)(kTB + 1) * Wc + 1, 0);            // exclusive prefix sums over the five cell rows
+    for (size_t c = 0; c + 1 < off.size(); ++c) off[c + 1] = off[c] + (int)((c * 2654435761u >> 7) % 5u) * (int)(c % 3u != 1u);
+    auto run_end = [&](int r, int cx) { return off[(size_t)r * Wc + std::min(cx, Wc)]; };
+    auto describe = [&](int bx) {
+        TileDesc td = {};
+        for (int r = 0; r <= kTB; ++r) {
+            td.first[r] = 1000 + run_end(r, kTB * bx);
+            td.cnt[r] = run_end(r, kTB * bx + kTB + 1) - run_end(r, kTB * bx);
+        }
+        td.hw = (8u << 16) | (uint32_t)Wl; td.lstart = 7; td.byx = (1u << 16) | (uint32_t)bx; td.parts = 1;
+        return td;
+    };
+    int wrong = 0;
+    for (int b0 = 0; b0 < nbx4; ++b0)
+        for (int b1 = 0; b1 < nbx4; ++b1) {
+            const TileDesc t0 = describe(b0), t1 = describe(b1);
+            int want[kTB + 1], n = 0;
+            for (int r = 0; r <= kTB; ++r) n += want[r] = run_end(r, kTB * b0 + 2 * kTB + 1) - run_end(r, kTB * b0);
+            const bool couple = b0 % 2 == 0 && b1 == b0 + 1;
+            for (int chunk = n - 1; chunk <= n + 1; ++chunk) {
+                TileDesc m;
+                const bool ok = tile_pair(t0, t1, chunk, m);
+                if (ok != (couple && n <= chunk)) ++wrong;
+                if (!ok) continue;
+                for (int r = 0; r <= kTB; ++r)
+                    if (m.first[r] != t0.first[r] || m.cnt[r] != want[r]) ++wrong;
+                if (m.hw != t0.hw || m.lstart != t0.lstart || m.byx != t0.byx) ++wrong;
+            }
+            if (!couple) continue;
+            TileDesc m, cut0 = t0, cut1 = t1, row = t1, lvl = t1;
+            cut0.parts = 2; cut1.parts = 2; row.byx += 1u << 16; lvl.lstart += 1;
+            if (tile_pair(cut0, t1, n, m) || tile_pair(t0, cut1, n, m) || tile_pair(t0, row, n, m) || tile_pair(t0, lvl, n, m)) ++wrong;
+        }
+    return wrong;
+}
+
 // Host-only self-check of the sort's tiling rules for ONE level (tests/test_plan_cpu.py sweeps it): the very
 // functions the device plan uses (level_tiling, tile_local_blocks, block_is_tile_local).  Returns 0 when
 // the tiles cover every cell exactly once within the counters' capacity AND every 4x4 block is planned exactly
-// once -- by the one tile that holds its five cell rows, or, on a seam, by the slice's last workgroup;
+// once -- by the one tile that holds its five cell rows, or, on a seam, by the slice's last workgroup -- AND (levels up to
+// 64 pixels wide) the reduce's rule for taking two blocks as one item holds on a block row of this width (pair_selfcheck);
 // else a positive count of what is wrong.  -1: the level owns no tile (empty / refused extents).
 extern "C" int mmfs_msda_plan_selfcheck(int64_t Hl, int64_t Wl, int nt_min)
 {
@@ -1518,6 +1564,7 @@ extern "C" int mmfs_msda_plan_selfcheck(int64_t Hl, int64_t Wl, int nt_min)
     if (n != lt.n || covered != (int64_t)Hc * Wc) ++wrong;
     for (int by = 0; by < lr.nby4; ++by)
         if (planned[(size_t)by] + (block_is_tile_local(lr, by) ? 0 : 1) != 1) ++wrong;
+    if (Wl <= 64) wrong += pair_selfcheck((int)Wl, lr.nbx4);
     return wrong;
 }
 

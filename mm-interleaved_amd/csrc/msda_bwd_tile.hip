@@ -38,6 +38,19 @@
 // Semantics that differ from the gather kernels, by construction of a matrix product: a non-finite
 // grad_out element reaches all 16 pixels of the blocks its sample touches (0 * Inf = NaN), not only
 // the sample's four corners.  Finite inputs: same products, fp32 sums in a different order.
+//
+// Pairs (MMFS_TILE_PAIR, default on).  Most lists are short -- the 64x64 level's average 97 records, six steps -- and a
+// work item's fixed latency (descriptor, first records, first rows, epilogue: ~10 k clocks) is then half of it.  Two
+// whole blocks (by, bx), (by, bx + 1), bx even, whose lists together fit one item are ONE item of 4 x 8 pixels
+// (tile_pair, msda_bwd_block.h: the pair's five runs are contiguous again): one prologue and one epilogue for both, and
+// the cells 4 bx + 4 the two share are walked once (45 cell visits for 32 pixels, 1.41 rows per sample).  The grid is
+// unchanged: the even block's wave does the pair, the odd block's wave evaluates the same test and returns (a slice's odd
+// block indices are dispatched before its even ones: see the kernel).  M = 32 is
+// then 32 pixels: the hi and the lo parts are two A tiles, built one after the other in the SAME kilobyte of LDS (the
+// workgroup stays at 10 KB, 16 per CU at D = 128), two products per 32 channels into the same accumulator, no hi + lo
+// addition in the epilogue, whose 16-row staging area is used twice.  Everything else -- cut lists, the odd last block
+// of a row, a partner that does not qualify, the queue of extra items -- takes the path above unchanged.  A non-finite
+// grad_out element then reaches the 32 pixels of the pair its sample touches, not only the 16 of a block.
 #include "msda_bwd_block.h"
 #include "msda_env.h"
 #include "msda_launch.h"
@@ -47,7 +60,7 @@
 #define MMFS_PROF_COUNTERS g_tile_prof
 #endif
 #define MMFS_PROF_SLOTS 32768
-#define MMFS_PROF_N 12
+#define MMFS_PROF_N 16
 #define MMFS_PROF_LANE (threadIdx.x == 0)
 #include "msda_prof.h"
 
@@ -159,7 +172,8 @@ struct ItemArgs { int b, h, part; bool whole, partial_out; uint32_t pidx; };
 //   ... | rows(4j+1) recs(j+1) | rows(4j+2) | rows(4j+3) | rows(4j+4) | rows(4j+5) recs(j+2) | ...
 //   step 4j+1 needs rows(4j+1): issued after it: recs(j+1), two requests -> vmcnt(2);  step 4j+3 needs
 //   rows(4j+3) and recs(j+1) (for rows(4j+4)) -> vmcnt(0);  the others: vmcnt(0).
-template <typename T, int D>
+// PAIR: the item is a pair of blocks, td the merged descriptor (tile_pair): 4 x 8 pixels, always whole.
+template <typename T, int D, bool PAIR>
 __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__restrict__ grad_value,
                                           const TileReduceArgs &a, const Dims &d, const TileDesc &td, const ItemArgs &it,
                                           uint32_t *arrived_ctr, unsigned char *__restrict__ lds)
@@ -168,6 +182,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
     typedef TileMma<T> M;
     unsigned char *rows = lds, *recs = lds + G::ROWS_BYTES, *atile = recs + G::REC_BYTES;
     const int lane = threadIdx.x;
+    constexpr int TW = PAIR ? 2 * kTB : kTB;                      // pixel columns of the item
     PROF_DECL;
     const int Hl = (int)(td.hw >> 16), Wl = (int)(td.hw & 0xffffu);
     const int by = (int)(td.byx >> 16), bx = (int)(td.byx & 0xffffu);
@@ -183,6 +198,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
     const int rounds = (nks + 3) / 4;
     if (__builtin_amdgcn_readfirstlane(n) >= 0) PROF(0);          // descriptor arrived
     PROF_COUNT(8, 1); PROF_COUNT(9, rounds); PROF_COUNT(10, nks);
+    if (PAIR) { PROF_COUNT(12, 1); PROF_COUNT(13, nks); }
 
     const uint32_t HDB = (uint32_t)(d.H * d.D) * (uint32_t)sizeof(T);            // bytes between consecutive queries
     const T *gslice = grad_out + ((int64_t)it.b * d.Nq * d.H + it.h) * d.D;
@@ -251,6 +267,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
             constexpr int S = decltype(stage)::value;
             // ---- weight tile: 16 records x 4 corners, one weight per lane
             reinterpret_cast<uint4 *>(atile)[lane] = make_uint4(0u, 0u, 0u, 0u);
+            s16x8 A, A2;
             {
                 const uint32_t *rb = reinterpret_cast<const uint32_t *>(recs + (j & 1) * (kRecBatch * 8)) + S * kKS + wr;
                 const uint32_t w0 = rb[0], w1 = rb[kRecBatch];
@@ -262,15 +279,30 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
                 const int iy = (int)yf + iy0, ix = (int)xf + ix0;
                 const float wy = (wc >> 1) ? fy : 1.f - fy, wx = (wc & 1) ? fx : 1.f - fx;
                 const float wgt = wy * wx * av;
-                if (kKS * (4 * j + S) + wr < cnt && (unsigned)iy < (unsigned)kTB && (unsigned)ix < (unsigned)kTB) {
-                    uint16_t hi, lo;
-                    M::split(wgt, hi, lo);
-                    const int m = iy * kTB + ix;
-                    reinterpret_cast<uint16_t *>(atile)[m * kKS + wr] = hi;
-                    reinterpret_cast<uint16_t *>(atile)[(16 + m) * kKS + wr] = lo;
+                const bool mine = kKS * (4 * j + S) + wr < cnt && (unsigned)iy < (unsigned)kTB && (unsigned)ix < (unsigned)TW;
+                uint16_t hi, lo;
+                M::split(wgt, hi, lo);
+                const int m = iy * TW + ix;
+                if (!PAIR) {
+                    if (mine) {
+                        reinterpret_cast<uint16_t *>(atile)[m * kKS + wr] = hi;
+                        reinterpret_cast<uint16_t *>(atile)[(16 + m) * kKS + wr] = lo;
+                    }
+                    A = *reinterpret_cast<const s16x8 *>(atile + a_rd);
+                    A2 = A;
+                } else {
+                    // 32 pixels: the hi tile, read, then the lo parts over the same elements (the rest stays zero).  A wave's
+                    // LDS accesses complete in order; the compiler must not move them across each other either
+                    if (mine) reinterpret_cast<uint16_t *>(atile)[m * kKS + wr] = hi;
+                    asm volatile("" ::: "memory");
+                    A = *reinterpret_cast<const s16x8 *>(atile + a_rd);
+                    asm volatile("" ::: "memory");
+                    if (mine) reinterpret_cast<uint16_t *>(atile)[m * kKS + wr] = lo;
+                    asm volatile("" ::: "memory");
+                    A2 = *reinterpret_cast<const s16x8 *>(atile + a_rd);
+                    asm volatile("" ::: "memory");
                 }
             }
-            const s16x8 A = *reinterpret_cast<const s16x8 *>(atile + a_rd);
             // ---- the step's rows as B operands, one MFMA per 32 channels
             const unsigned char *slot = rows + (S % 2) * G::SLOT;
 #pragma unroll
@@ -283,6 +315,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
                     B[4 * t] = v[0]; B[4 * t + 1] = v[1]; B[4 * t + 2] = v[2]; B[4 * t + 3] = v[3];
                 }
                 acc[nb] = M::run(A, B, acc[nb]);
+                if (PAIR) acc[nb] = M::run(A2, B, acc[nb]);
             }
         };
         using S0 = std::integral_constant<int, 0>;
@@ -311,103 +344,118 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
             issue_rows(j + 1, S0{});                              // rows(4j + 4): first step of batch j + 1
             if (4 * j + 3 < nks) multiply(j, S3{});
         }
+#ifdef MMFS_PROFILE_TILE
+        if (PAIR) prof_t[14] += __builtin_readcyclecounter() - prof_c;
+#endif
         PROF(3);                                                 // rounds
         MMFS_WAIT_VM(0);                                          // (requests past the end of the list)
         PROF(4);
     }
 
-    // ---- epilogue: hi + lo rows; lane pairs exchange one value so that every lane holds whole dwords
+    // ---- epilogue: hi + lo rows (a pair: 16 of its 32 pixel rows at a time, nothing to add); lane pairs exchange one
+    // value so that every lane holds whole dwords
     const bool odd = lane & 1;
+    const bool partial = !PAIR && it.partial_out;
     const int ch0 = (lane & 31) & ~1;
     constexpr int PITCH = G::RB + 16;                             // staging pitch: rows 8 apart in different banks
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int pa = mfma_row32(r, lane), pb = mfma_row32(r + 4, lane);      // pixels 0..15 of the block
-        const int p = odd ? pb : pa;
+    for (int hf = 0; hf < (PAIR ? 2 : 1); ++hf) {
+        if (PAIR) asm volatile("" ::: "memory");                      // (the staging area is read, then written again)
 #pragma unroll
-        for (int nb = 0; nb < G::NB; ++nb) {
-            const float va = acc[nb][r] + acc[nb][r + 8], vb = acc[nb][r + 4] + acc[nb][r + 12];
-            const float recv = __shfl_xor(odd ? va : vb, 1, 64);
-            const float lo_ch = odd ? recv : va, hi_ch = odd ? vb : recv;       // channels ch0, ch0 + 1 of pixel p
-            const int ch = nb * 32 + ch0;
-            if (it.partial_out) {
-                // (written through, agent scope: another item of the block adds the tiles up within this launch)
-                float *o = a.tpartials + ((int64_t)it.pidx * (kTB * kTB) + p) * D + ch;
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(o),
-                                   ((unsigned long long)__float_as_uint(hi_ch) << 32) | (unsigned long long)__float_as_uint(lo_ch),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                *reinterpret_cast<uint32_t *>(rows + p * PITCH + ch * 2) = M::pack2(lo_ch, hi_ch);
+        for (int r = 0; r < 4; ++r) {
+            const int pa = mfma_row32(r, lane), pb = mfma_row32(r + 4, lane);      // pixels 0..15 of the block (of the pair's half)
+            const int p = odd ? pb : pa;
+#pragma unroll
+            for (int nb = 0; nb < G::NB; ++nb) {
+                const float va = PAIR ? acc[nb][8 * hf + r] : acc[nb][r] + acc[nb][r + 8];
+                const float vb = PAIR ? acc[nb][8 * hf + r + 4] : acc[nb][r + 4] + acc[nb][r + 12];
+                const float recv = __shfl_xor(odd ? va : vb, 1, 64);
+                const float lo_ch = odd ? recv : va, hi_ch = odd ? vb : recv;       // channels ch0, ch0 + 1 of pixel p
+                const int ch = nb * 32 + ch0;
+                if (partial) {
+                    // (written through, agent scope: another item of the block adds the tiles up within this launch)
+                    float *o = a.tpartials + ((int64_t)it.pidx * (kTB * kTB) + p) * D + ch;
+                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(o),
+                                       ((unsigned long long)__float_as_uint(hi_ch) << 32) | (unsigned long long)__float_as_uint(lo_ch),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    *reinterpret_cast<uint32_t *>(rows + p * PITCH + ch * 2) = M::pack2(lo_ch, hi_ch);
+                }
             }
         }
-    }
-    if (it.partial_out) {
-        // A block of several items: the item that arrives last adds the partial tiles up (in tile order,
-        // whoever is last) and rounds.  The tiles are stored and read with agent-scope accesses and the
-        // stores are drained before the counter moves: no L2 write-back (a release fence here writes
-        // back every dirty grad_value line of the XCD, measured: the kernel twice as slow).
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        uint32_t prev = 0u;
-        if (lane == 0) prev = __hip_atomic_fetch_add(arrived_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        prev = (uint32_t)__builtin_amdgcn_readfirstlane((int)prev);
-        if (prev == td.parts - 1u) {
-            constexpr int CPL = D >= 128 ? 2 : 1;                  // channels per lane
-            const int ch = lane * CPL;
-            float s[kTB * kTB][CPL];
+        if (partial) {
+            // A block of several items: the item that arrives last adds the partial tiles up (in tile order,
+            // whoever is last) and rounds.  The tiles are stored and read with agent-scope accesses and the
+            // stores are drained before the counter moves: no L2 write-back (a release fence here writes
+            // back every dirty grad_value line of the XCD, measured: the kernel twice as slow).
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            uint32_t prev = 0u;
+            if (lane == 0) prev = __hip_atomic_fetch_add(arrived_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            prev = (uint32_t)__builtin_amdgcn_readfirstlane((int)prev);
+            if (prev == td.parts - 1u) {
+                constexpr int CPL = D >= 128 ? 2 : 1;                  // channels per lane
+                const int ch = lane * CPL;
+                float s[kTB * kTB][CPL];
 #pragma unroll
-            for (int p = 0; p < kTB * kTB; ++p)
+                for (int p = 0; p < kTB * kTB; ++p)
 #pragma unroll
-                for (int k = 0; k < CPL; ++k) s[p][k] = 0.f;
-            if (ch < D) {
-                for (uint32_t c = 0; c < td.parts; ++c) {
-                    const float *src = a.tpartials + (int64_t)(td.pbase + c) * (kTB * kTB) * D + ch;
+                    for (int k = 0; k < CPL; ++k) s[p][k] = 0.f;
+                if (ch < D) {
+                    for (uint32_t c = 0; c < td.parts; ++c) {
+                        const float *src = a.tpartials + (int64_t)(td.pbase + c) * (kTB * kTB) * D + ch;
+#pragma unroll
+                        for (int p = 0; p < kTB * kTB; ++p) {
+                            if (CPL == 2) {
+                                const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(src + p * D),
+                                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                s[p][0] += __uint_as_float((uint32_t)v); s[p][CPL - 1] += __uint_as_float((uint32_t)(v >> 32));
+                            } else {
+                                s[p][0] += __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(src + p * D),
+                                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                            }
+                        }
+                    }
 #pragma unroll
                     for (int p = 0; p < kTB * kTB; ++p) {
-                        if (CPL == 2) {
-                            const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(src + p * D),
-                                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            s[p][0] += __uint_as_float((uint32_t)v); s[p][CPL - 1] += __uint_as_float((uint32_t)(v >> 32));
-                        } else {
-                            s[p][0] += __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(src + p * D),
-                                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                        const int y = kTB * by + (p >> 2), x = kTB * bx + (p & 3);
+                        if (y < Hl && x < Wl) {
+                            T *o = grad_value + (((int64_t)it.b * d.S + td.lstart + y * Wl + x) * d.H + it.h) * d.D + ch;
+                            if (CPL == 2) *reinterpret_cast<uint32_t *>(o) = M::pack2(s[p][0], s[p][CPL - 1]);
+                            else o[0] = (T)s[p][0];
                         }
                     }
                 }
-#pragma unroll
-                for (int p = 0; p < kTB * kTB; ++p) {
-                    const int y = kTB * by + (p >> 2), x = kTB * bx + (p & 3);
-                    if (y < Hl && x < Wl) {
-                        T *o = grad_value + (((int64_t)it.b * d.S + td.lstart + y * Wl + x) * d.H + it.h) * d.D + ch;
-                        if (CPL == 2) *reinterpret_cast<uint32_t *>(o) = M::pack2(s[p][0], s[p][CPL - 1]);
-                        else o[0] = (T)s[p][0];
-                    }
-                }
             }
-        }
-    } else {
-        // the block's 16 rows leave as whole 16-byte chunks, LPR consecutive lanes per row
+        } else {
+            // the block's 16 rows (the 16 of this half of a pair's 4 x 8) leave as whole 16-byte chunks, LPR consecutive lanes per row
+            if (PAIR) asm volatile("" ::: "memory");
 #pragma unroll
-        for (int i = 0; i < kTB * kTB * G::LPR / 64; ++i) {
-            const int c = i * 64 + lane, p = c / G::LPR, chunk = c % G::LPR;
-            const uint4 v = *reinterpret_cast<const uint4 *>(rows + p * PITCH + chunk * 16);
-            const int y = kTB * by + (p >> 2), x = kTB * bx + (p & 3);
-            if (y < Hl && x < Wl) {
-                T *o = grad_value + (((int64_t)it.b * d.S + td.lstart + y * Wl + x) * d.H + it.h) * d.D + chunk * 8;
+            for (int i = 0; i < kTB * kTB * G::LPR / 64; ++i) {
+                const int c = i * 64 + lane, p = c / G::LPR, chunk = c % G::LPR;
+                const uint4 v = *reinterpret_cast<const uint4 *>(rows + p * PITCH + chunk * 16);
+                const int pp = 16 * hf + p;
+                const int y = kTB * by + pp / TW, x = kTB * bx + pp % TW;
+                if (y < Hl && x < Wl) {
+                    T *o = grad_value + (((int64_t)it.b * d.S + td.lstart + y * Wl + x) * d.H + it.h) * d.D + chunk * 8;
 #ifndef MMFS_TILE_PLAIN_STORE
-                store16_stream(o, v);              // (grad_value is not read again in the step: r03i, 0.4604 -> 0.4431 ms)
+                    store16_stream(o, v);              // (grad_value is not read again in the step: r03i, 0.4604 -> 0.4431 ms)
 #else
-                *reinterpret_cast<uint4 *>(o) = v;
+                    *reinterpret_cast<uint4 *>(o) = v;
 #endif
+                }
             }
         }
     }
 #ifdef MMFS_PROFILE_TILE
     {   // epilogue clocks and counts by kind of item: whole blocks / parts that leave a partial tile
         const unsigned long long tn = __builtin_readcyclecounter();
-        if (it.partial_out) { prof_t[6] += tn - prof_c; prof_t[7] += 1; } else { prof_t[11] += tn - prof_c; }
+        if (partial) { prof_t[6] += tn - prof_c; prof_t[7] += 1; } else { prof_t[11] += tn - prof_c; }
     }
 #endif
     PROF(5);                                                     // epilogue issued
+#ifdef MMFS_PROFILE_TILE
+    if (PAIR) for (int i = 0; i < 6; ++i) prof_t[15] += prof_t[i];          // all clocks of the paired items
+#endif
     PROF_FLUSH();
 }
 
@@ -419,7 +467,7 @@ __device__ __forceinline__ void tile_item(const T *__restrict__ grad_out, T *__r
 template <typename T, int D>
 __global__ void __launch_bounds__(64, 4)
 msda_bwd_tile_reduce(const T *__restrict__ grad_out, T *__restrict__ grad_value, const TileReduceArgs a,
-                     const Dims d, const int blocks_grid, const int extra_grid)
+                     const Dims d, const int blocks_grid, const int extra_grid, const int pair)
 {
     typedef TileGeom<D> G;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[G::LDS_BYTES];
@@ -440,17 +488,40 @@ msda_bwd_tile_reduce(const T *__restrict__ grad_out, T *__restrict__ grad_value,
         it.part = (int)ti.part; it.whole = false; it.partial_out = true; it.pidx = ti.pidx;
         TileDesc *tdp = a.tdesc + (bh * a.blocks_bound + ti.blk);
         const TileDesc td = *tdp;
-        tile_item<T, D>(grad_out, grad_value, a, d, td, it, &tdp->arrived, lds);
+        tile_item<T, D, false>(grad_out, grad_value, a, d, td, it, &tdp->arrived, lds);
         return;
     }
     j -= extra_grid;
     const int nblk = a.hdr->n_blocks4;
     if (j >= nblk) return;
-    const int blk = nblk - 1 - j;                          // coarse levels (long lists) first
+    int blk = nblk - 1 - j;                                // coarse levels (long lists) first
+    if (pair) {
+        // ... the blocks of odd index before those of even index, each kind coarse levels first.  The second wave of a
+        // pair has nothing to do, and a block's index is its column up to the parity of its level's first index and width:
+        // in index order, waves that work and waves that return at once alternate.  Measured at the north star
+        // (profiles/tile_pair.md): the reduce 167 us in that order -- the waves' summed clocks down by a fifth, the wave
+        // slots half empty -- against 128 us without pairs and 118 us in this order.  (Supposed, not measured: an XCD's
+        // shader engines take workgroups in turn, so one half of them was handed the idle waves only.)
+        const int nodd = nblk / 2;
+        blk = j < nodd ? 2 * (nodd - 1 - j) + 1 : 2 * (nblk - 1 - j);
+    }
     TileDesc *tdp = a.tdesc + (bh * a.blocks_bound + blk);
     const TileDesc td = *tdp;
+    if (pair) {
+        // both neighbours' descriptors (which of them is the partner is in td itself); the wave of the even block does the
+        // pair, the wave of the odd block finds the same answer and has nothing to do
+        const TileDesc tl = tdp[blk > 0 ? -1 : 0], tr = tdp[blk + 1 < nblk ? 1 : 0];
+        const bool second = td.byx & 1u;
+        TileDesc tm;
+        if (tile_pair(second ? tl : td, second ? td : tr, tile_chunk(d), tm)) {
+            if (second) return;
+            it.part = 0; it.whole = true; it.partial_out = false; it.pidx = 0;
+            tile_item<T, D, true>(grad_out, grad_value, a, d, tm, it, &tdp->arrived, lds);
+            return;
+        }
+    }
     it.part = 0; it.whole = td.parts <= 1; it.partial_out = td.parts > 1; it.pidx = td.pbase;
-    tile_item<T, D>(grad_out, grad_value, a, d, td, it, &tdp->arrived, lds);
+    tile_item<T, D, false>(grad_out, grad_value, a, d, td, it, &tdp->arrived, lds);
 }
 
 template <typename T, int D>
@@ -463,7 +534,7 @@ hipError_t launch_tile(const void *go, void *gv, const TileReduceArgs &a, const 
     const int64_t items = (int64_t)d.B * d.H * ((int64_t)blocks_grid + cap_extra);
     if (items > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL((msda_bwd_tile_reduce<T, D>), dim3((unsigned)items), dim3(64), 0, st,
-                       (const T *)go, (T *)gv, a, d, blocks_grid, (int)cap_extra);
+                       (const T *)go, (T *)gv, a, d, blocks_grid, (int)cap_extra, knob_int(K_TILE_PAIR, 1) != 0);
     return hipGetLastError();
 }
 template <typename T>

@@ -13,6 +13,7 @@ enum Knob {
     K_VALUE_ALGO, K_PREPARE_IN_TAPS,
     K_NT_MIN, K_SORT_WINDOW_KB, K_SORT_ROUNDS, K_SORT_SMALL, K_SORT_MANY_POINTS, K_SORT_HGROUP, K_SORT_REPACK, K_SORT_WIDE,
     K_SAMPLE_DECODE, K_LIN_ROWS, K_LIN_UNROLL, K_LIN_EARLY, K_QUERY_LDS_KB, K_NORM_BWD_GRID,
+    K_TILE_PAIR,
     K_COUNT
 };
 

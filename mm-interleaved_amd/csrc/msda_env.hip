@@ -39,6 +39,7 @@ const KnobInfo kKnobs[K_COUNT] = {
     {"MMFS_LIN_EARLY", "mmfs_linear_small: 0: no early issue of the next weight pieces"},
     {"MMFS_QUERY_LDS_KB", "mmfs_query_prep: LDS budget of a workgroup"},
     {"MMFS_NORM_BWD_GRID", "RMS-norm backward: workgroups"},
+    {"MMFS_TILE_PAIR", "0: the matrix-core grad_value reduce takes every 4x4 block as an item of its own (no pairs of neighbouring whole blocks)"},
 };
 
 struct Values {

@@ -36,3 +36,13 @@ print("  total %.0f clk per item" % (sum(v[:6]) / items))
 npart = max(v[7], 1)
 print("  epilogue of the %.0f items per call that leave a partial tile: %.0f clk each; of the %.0f whole blocks: %.0f clk each"
       % (v[7] / n, v[6] / npart, (v[8] - v[7]) / n, v[11] / max(v[8] - v[7], 1)))
+# pairs of neighbouring whole blocks taken as one item (MMFS_TILE_PAIR): how many, their step and fixed clocks
+nb4 = B * H * sum(((int(h) + 3) // 4) * ((int(w) + 3) // 4) for h, w in shapes.tolist())
+pairs, psteps = v[12], max(v[13], 1)
+print("  pairs per call %.0f = %.1f %% of the %d blocks; a pair: %.2f steps, %.0f clk per step, %.0f clk fixed, %.0f clk in all"
+      % (pairs / n, 200.0 * pairs / n / nb4, nb4, v[13] / max(pairs, 1), v[14] / psteps, (v[15] - v[14]) / max(pairs, 1),
+         v[15] / max(pairs, 1)))
+single = max(items - pairs, 1)
+print("  the other %.0f items: %.2f steps, %.0f clk per step, %.0f clk fixed"
+      % ((items - pairs) / n, (v[10] - v[13]) / single, (v[3] - v[14]) / max(v[10] - v[13], 1),
+         (sum(v[:6]) - v[3] - (v[15] - v[14])) / single))
