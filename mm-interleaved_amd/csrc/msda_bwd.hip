@@ -301,12 +301,13 @@ copy_f32_kernel(const float *__restrict__ src, float *__restrict__ dst, const in
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) dst[i] = src[i];
 }
 
-// dst = (T) src, 4 elements per thread
+// dst = (T) src, 4 elements per thread where dst takes 8-byte stores -- the float-atomic backward hands it a grad_value that
+// is only element aligned when D * es is no multiple of 16 (msda_capi.hip, row_align): one element per thread then
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 cast_kernel(const float *__restrict__ src, T *__restrict__ dst, const int64_t n)
 {
-    const int64_t n4 = n / 4;
+    const int64_t n4 = (reinterpret_cast<uintptr_t>(dst) & 7) == 0 ? n / 4 : 0;
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(src)[i];

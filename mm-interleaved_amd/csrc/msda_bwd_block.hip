@@ -1035,7 +1035,9 @@ uint32_t sort_window_bytes(const Dims &d, const TileParams &tp, bool compact)
     if (tp.nt_min > 1) want = want / tp.nt_min + want / tp.nt_min / 4;
     if (const char *e = knob_str(K_SORT_WINDOW_KB)) want = std::min<int64_t>(atoll(e) * 1024, kMaxSortWindow);
     // more records than the largest window: placed window by window while that takes few rounds (the SD block's
-    // 32768 samples per level: two), else the direct path (MMFS_SORT_ROUNDS=0: always the direct path)
+    // 32768 samples per level: two), else the direct path (MMFS_SORT_ROUNDS=0: always the direct path -- except with
+    // Dims::taps_sorted, whose floor is 16 bytes above a tile's cells so that the kept scan stays: the knob then selects that
+    // scan over a window of kMaxTileCells * 4 + 16 bytes, some 2560 compact records a round; tests/test_knob_routes_gpu.py holds both)
     const int max_rounds = knob_int(K_SORT_ROUNDS, 4);
     if (want > kMaxSortWindow) return (kWindowRounds && want <= (int64_t)max_rounds * kMaxSortWindow) ? kMaxSortWindow : floor_bytes;
     return (uint32_t)std::max<int64_t>(floor_bytes, (want + 15) / 16 * 16);

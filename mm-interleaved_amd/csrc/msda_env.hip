@@ -27,7 +27,7 @@ const KnobInfo kKnobs[K_COUNT] = {
     {"MMFS_PREPARE_IN_TAPS", "0: the grad_value half's opening job is a launch of its own, not hosted by msda_taps_mma"},
     {"MMFS_NT_MIN", "cell sort: tiles per level at least"},
     {"MMFS_SORT_WINDOW_KB", "cell sort: LDS window"},
-    {"MMFS_SORT_ROUNDS", "cell sort: most window rounds before the two-scan path (0: always that path)"},
+    {"MMFS_SORT_ROUNDS", "cell sort: most window rounds before the windowless path (0: always that path; with grad_loc / grad_attn from the sort's records: the kept scan over the smallest window)"},
     {"MMFS_SORT_SMALL", "0: always 1024-lane sort workgroups (no 256 / 512-lane variants for many small slices)"},
     {"MMFS_SORT_MANY_POINTS", "0: no grouped scan for more than two 16-byte vectors of locations per query"},
     {"MMFS_SORT_HGROUP", "cell sort: heads that share a workgroup's sector reads"},

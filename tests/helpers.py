@@ -370,3 +370,305 @@ def worst_ratio(got, ref, bound, skip=None):
     ratio = torch.where(pos, err / torch.where(pos, bound, zero + 1.0), torch.where(err > 0, inf, zero))
     k = int(ratio.reshape(-1).argmax())
     return float(ratio.reshape(-1)[k]), k, float(err.reshape(-1)[k]), float(bound.reshape(-1)[k])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Placement: operands at the least alignment an entry point accepts, and outputs between guard bands.
+#
+# Every tensor torch's allocator hands out is 512-byte aligned and has slack behind it, so a branch a kernel takes on a
+# pointer's alignment never runs, and a store a few elements outside an output lands in memory nobody looks at.
+# ``placed`` puts a tensor at a chosen byte offset from a 256-byte boundary, inside a buffer the test owns, between two
+# guard bands; ``guarded_allocations`` does the same to what the code under test allocates.
+#
+# What the guards catch: a store within GUARD_BYTES before or behind a placed tensor (the band is compared byte for
+# byte), and -- with 0xFF input guards, NaN in every floating type here and -1 in the integer tables -- a read outside
+# an input that reaches a result (the result then differs from the run on ordinary allocations).  What they do not
+# catch: a store further out than GUARD_BYTES (64 KiB is a condition of the check, not a measurement of how far a stray
+# store can go), a stray store that writes the guard's own byte value, and a stray read whose value is multiplied away
+# or never used.
+# ---------------------------------------------------------------------------------------------------------------------
+GUARD_BYTES = 64 * 1024
+PLACE_ALIGN = 256
+_raw_empty = torch.empty               # (guarded_allocations replaces torch.empty: the buffers themselves come from this)
+INPUT_GUARD, OUTPUT_GUARD = 0xFF, 0xA5
+
+
+class Placed:
+    """A tensor inside a guarded byte buffer: ``t`` the tensor, ``buf`` the whole buffer (uint8), ``lo`` / ``hi`` the
+    payload's byte range in it, ``fill`` the guards' byte, ``name`` what messages call it, ``before`` a copy of the
+    payload's bytes as they were put in (inputs) or None."""
+    __slots__ = ("t", "buf", "lo", "hi", "fill", "name", "before")
+
+    def __init__(self, t, buf, lo, hi, fill, name):
+        self.t, self.buf, self.lo, self.hi, self.fill, self.name, self.before = t, buf, lo, hi, fill, name, None
+
+    def payload(self):
+        return self.buf[self.lo:self.hi]
+
+
+def _place(shape, strides, dtype, device, lead, guard_fill, name):
+    """A guarded buffer and a tensor of ``shape`` / ``strides`` (None: contiguous) in it whose first element lies ``lead``
+    bytes past a PLACE_ALIGN boundary.  The payload is left as the guard byte."""
+    es = _raw_empty((), dtype=dtype).element_size()
+    assert lead >= 0 and lead % es == 0, f"{name}: a lead of {lead} bytes is no multiple of the {es}-byte element"
+    shape = tuple(int(s) for s in shape)
+    numel = int(np.prod(shape, dtype=np.int64)) if shape else 1
+    if strides is None:
+        span = numel
+    else:
+        span = 1 + sum((n - 1) * s for n, s in zip(shape, strides)) if numel else 0
+        assert span == numel, f"{name}: strides {strides} of shape {shape} are not dense"
+    nbytes = span * es
+    buf = _raw_empty(2 * GUARD_BYTES + PLACE_ALIGN + lead + nbytes, dtype=torch.uint8, device=device)
+    buf.fill_(guard_fill)
+    lo = GUARD_BYTES + (-(buf.data_ptr() + GUARD_BYTES)) % PLACE_ALIGN + lead
+    flat = buf[lo:lo + nbytes].view(dtype)
+    t = flat.view(shape) if strides is None else flat.as_strided(shape, strides)
+    assert numel == 0 or (t.data_ptr() - lead) % PLACE_ALIGN == 0
+    return Placed(t, buf, lo, lo + nbytes, guard_fill, name)
+
+
+def placed(t, lead=0, guard_fill=INPUT_GUARD, device=None, name="tensor"):
+    """-> Placed: a contiguous copy of ``t`` (on ``device``, default ``t``'s) that starts ``lead`` bytes past a 256-byte
+    boundary, with at least GUARD_BYTES of ``guard_fill`` bytes on either side (0xFF for inputs, 0xA5 for outputs).  The
+    copy is ``.t``; its bytes as put in are kept for ``assert_payload_unchanged``.  A store further than GUARD_BYTES from
+    the tensor is not seen (above)."""
+    src = t.detach().contiguous()
+    h = _place(src.shape, None, src.dtype, torch.device(device) if device is not None else src.device, lead, guard_fill, name)
+    h.t.copy_(src)
+    h.before = h.payload().clone()
+    return h
+
+
+def _first_bad(band, fill):
+    bad = (band != fill).nonzero()
+    return None if bad.numel() == 0 else (int(bad[0]), int(bad[-1]), int(bad.numel()))
+
+
+def guard_damage(h):
+    """None, or a sentence on where the guards of ``h`` no longer hold their byte."""
+    below = _first_bad(h.buf[:h.lo], h.fill)
+    above = _first_bad(h.buf[h.hi:], h.fill)
+    msgs = []
+    if below is not None:
+        msgs.append(f"{below[2]} byte(s) changed BEFORE the start, the nearest {h.lo - below[1]} byte(s) before it")
+    if above is not None:
+        msgs.append(f"{above[2]} byte(s) changed PAST the end, the nearest {above[0]} byte(s) past it")
+    return "; ".join(msgs) or None
+
+
+def guards_intact(h):
+    """Both guard bands of ``h`` (a Placed) still hold their byte, compared byte for byte."""
+    return guard_damage(h) is None
+
+
+def assert_guards_intact(*handles):
+    bad = [f"{h.name}: {d}" for h in handles for d in [guard_damage(h)] if d]
+    assert not bad, "written outside a tensor: " + " | ".join(bad)
+
+
+def assert_payload_unchanged(*handles):
+    """Every placed INPUT holds, bit for bit, what was put in."""
+    for h in handles:
+        diff = (h.payload() != h.before).nonzero()
+        es = h.t.element_size()
+        assert diff.numel() == 0, (f"input {h.name} {tuple(h.t.shape)} was modified: {int(diff.numel())} byte(s), the first "
+                                   f"in element {int(diff[0]) // es}")
+
+
+def _bytes(t):
+    return t.detach().contiguous().reshape(-1).view(torch.uint8) if t.numel() else t.detach().reshape(-1).view(torch.uint8)
+
+
+def assert_bit_equal(got, want, name):
+    """Same shape, type and bytes (NaN payloads and signed zeros included)."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {tuple(got.shape)} {got.dtype} vs {tuple(want.shape)} {want.dtype}"
+    diff = (_bytes(got) != _bytes(want).to(got.device)).nonzero()
+    if diff.numel():
+        k = int(diff[0]) // got.element_size()
+        g, w = got.detach().contiguous().reshape(-1)[k], want.detach().contiguous().reshape(-1)[k]
+        raise AssertionError(f"{name}: {len(set((diff.reshape(-1) // got.element_size()).tolist()))} element(s) differ, the first "
+                             f"at flat index {k}: {g.item()!r} vs {w.item()!r}")
+
+
+def poison_left(t):
+    """How many elements of ``t`` still hold ``poison``'s pattern (NaN counts for the floating types: use on results that
+    are finite)."""
+    if t.numel() == 0:
+        return 0
+    t = t.detach()
+    if t.is_floating_point():
+        if t.element_size() == 1:
+            return int((t.contiguous().view(torch.uint8) == 0xFF).sum())
+        return int(torch.isnan(t).sum())
+    ref = _raw_empty((), dtype=t.dtype)
+    _fill_poison(ref)
+    return int((t == ref.to(t.device)).sum())
+
+
+def assert_no_poison(t, name):
+    n = poison_left(t)
+    assert n == 0, (f"{name} {tuple(t.shape)}: {n} element(s) hold the allocation's poison: nobody wrote them -- or, of a "
+                    f"floating type, a NaN read outside an input's extent reached them")
+
+
+class GuardedAllocations:
+    """What ``guarded_allocations`` recorded: ``records`` (a Placed per allocation it placed, named by the allocating
+    line), ``passed_through`` (a description per allocation on the guarded device it could not place)."""
+
+    def __init__(self):
+        self.records, self.passed_through = [], []
+
+    @property
+    def pass_through_count(self):
+        return len(self.passed_through)
+
+    def assert_all_intact(self):
+        assert_guards_intact(*self.records)
+
+
+def _dense(shape, strides):
+    """The strides are a permutation of a contiguous layout: every element of the span is owned once."""
+    want = 1
+    for n, s in sorted(((n, s) for n, s in zip(shape, strides) if n != 1), key=lambda p: p[1]):
+        if s != want:
+            return False
+        want *= n
+    return True
+
+
+def _caller(depth=2):
+    import sys
+    f = sys._getframe(depth)
+    return f"{os.path.basename(f.f_code.co_filename)}:{f.f_lineno}"
+
+
+def guarded_allocations(monkeypatch, device="cuda"):
+    """For the rest of a test: torch.empty / torch.empty_like / torch.zeros / Tensor.new_zeros on a ``device``-type device
+    hand out tensors placed (lead 0) between OUTPUT_GUARD bands of GUARD_BYTES each -- the payload poisoned as ``poison``
+    does, zero for the two zeros forms -- and every one is recorded.  -> GuardedAllocations.  Allocations on other devices
+    (meta, and the CPU unless ``device="cpu"``), pinned ones and empty ones pass through untouched; one on the guarded
+    device whose layout is not dense (no such request exists in the package today) passes through and is counted.  A
+    dense non-default ``memory_format`` is reproduced with ``as_strided`` inside the buffer.  A store further than
+    GUARD_BYTES from its tensor is not seen."""
+    rec = GuardedAllocations()
+    kind = torch.device(device).type
+    orig = dict(empty=torch.empty, empty_like=torch.empty_like, zeros=torch.zeros, new_zeros=torch.Tensor.new_zeros)
+
+    def guard(r, zero, site):
+        if not isinstance(r, torch.Tensor) or r.device.type != kind or r.numel() == 0 or r.layout != torch.strided:
+            return r
+        if kind == "cpu" and r.is_pinned():
+            return r
+        what = f"{tuple(r.shape)} {str(r.dtype)[6:]} allocated at {site}"
+        dense = r.is_contiguous() or _dense(r.shape, r.stride())
+        if not dense or r.is_complex() or r.is_quantized:
+            rec.passed_through.append(what)
+            return r
+        with torch.no_grad():
+            h = _place(r.shape, None if r.is_contiguous() else r.stride(), r.dtype, r.device, 0, OUTPUT_GUARD, what)
+            h.t.zero_() if zero else _fill_poison(h.t)
+        if r.requires_grad:
+            h.t.requires_grad_(True)
+        rec.records.append(h)
+        return h.t
+
+    def wrap(name, zero):
+        fn = orig[name]
+
+        def patched(*a, **k):
+            if k.get("out") is not None:
+                return fn(*a, **k)
+            return guard(fn(*a, **k), zero, _caller())
+        patched.__name__ = name
+        return patched
+
+    monkeypatch.setattr(torch, "empty", wrap("empty", False))
+    monkeypatch.setattr(torch, "empty_like", wrap("empty_like", False))
+    monkeypatch.setattr(torch, "zeros", wrap("zeros", True))
+    monkeypatch.setattr(torch.Tensor, "new_zeros", wrap("new_zeros", True))
+    return rec
+
+
+def run_placed(monkeypatch, fn, inputs, leads=None, device="cuda", bit_equal=True, allowed_pass_through=(), writes=()):
+    """The whole yardstick around one call.  ``fn(**tensors)`` -> a tensor or a sequence of tensors (None entries allowed),
+    allocating its outputs and workspaces itself; ``inputs``: {name: tensor}.  Runs ``fn`` on ordinary allocations, then
+    on inputs placed (``leads[name]`` bytes past a 256-byte boundary, default 0) between 0xFF guards under
+    ``guarded_allocations``, and asserts: no guard of an input or of a recorded allocation changed; every input holds what
+    was put in (but those named in ``writes``: tensors the call updates in place, a cache); no returned element is left poisoned; nothing passed through unplaced but ``allowed_pass_through``
+    (descriptions, matched as substrings); and, with ``bit_equal``, every returned tensor equals the ordinary run's bit for
+    bit -- a read outside an input would meet NaN / -1.  -> (placed run's outputs, ordinary run's outputs, recorder)."""
+    sync = torch.cuda.synchronize if torch.device(device).type == "cuda" else (lambda: None)
+    as_list = lambda r: [r] if isinstance(r, torch.Tensor) else list(r)
+    plain = as_list(fn(**{k: v.to(device).clone() for k, v in inputs.items()}))
+    sync()
+    handles = {k: placed(v, (leads or {}).get(k, 0), INPUT_GUARD, device, name=k) for k, v in inputs.items()}
+    with monkeypatch.context() as m:
+        rec = guarded_allocations(m, device)
+        got = as_list(fn(**{k: h.t for k, h in handles.items()}))
+        sync()
+    assert_guards_intact(*handles.values())
+    rec.assert_all_intact()
+    assert_payload_unchanged(*[h for k, h in handles.items() if k not in writes])
+    stray = [w for w in rec.passed_through if not any(a in w for a in allowed_pass_through)]
+    assert not stray, f"allocations that could not be placed between guards: {stray}"
+    assert len(got) == len(plain)
+    for i, (g, w) in enumerate(zip(got, plain)):
+        if g is None or w is None:
+            assert g is None and w is None, f"output {i}: one run returned None"
+            continue
+        assert_no_poison(g, f"output {i}")
+        if bit_equal:
+            assert_bit_equal(g, w, f"output {i} (placed inputs and guarded allocations vs ordinary ones)")
+    return got, plain, rec
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The op's inputs of tests/test_placement_gpu.py, shared with tests/test_placement.py (which checks on the CPU what share
+# of their samples ``near_crossing`` leaves out of the grad_loc comparison).
+# ---------------------------------------------------------------------------------------------------------------------
+# the smallest shape with a ragged query tile (33 queries) and two levels, neither a multiple of the 4x4 block
+OP_SHAPE = dict(B=1, H=2, Nq=33, P=4, shapes=[(5, 7), (2, 3)])
+OP_SEED = 61
+OP_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+# head widths: 32 (every route of the backward), 128 (what the LDS-resident forwards take)
+OP_WIDTHS = (32, 128)
+MAX_LEFT_OUT = 0.01          # share of grad_loc's samples ``near_crossing`` may leave out, per case
+
+
+def op_inputs(dtype, D=32, seed=OP_SEED, loc_range=(-0.1, 1.1)):
+    s = OP_SHAPE
+    return make_inputs(s["B"], s["H"], D, s["Nq"], s["P"], s["shapes"], seed=seed, loc_range=loc_range, dtype=dtype)
+
+
+def hot_inputs(dtype, D=64):
+    """Every location of a slice within one cell of each level (the "point" distribution of tests/fuzz_op.py: loc in
+    [0.45, 0.47]).  On the 8 x 8 level that cell's footprint is pixels 3 and 4 in both directions, so it straddles the four 4x4
+    blocks that meet there: each of them gets all 6000 samples of a slice -- more than a work item's records (768 at D = 64:
+    csrc/msda_bwd_block.h ``tile_chunk``), so the blocks' lists are cut into chunks -- the backward workspace's data-dependent
+    writers."""
+    x = make_inputs(1, 2, D, 1500, 4, [(8, 8), (4, 4)], seed=5, dtype=dtype)
+    x["loc"] = (x["loc"] * 0.02 + 0.45).to(dtype).double()
+    return x
+
+
+def pair_inputs(dtype, D=32):
+    """One 4 x 8 level = one pair of whole 4x4 blocks (the smallest case of tests/test_tile_pair_gpu.py), the locations moved
+    onto a grid of 64ths plus 1/256: on 16-bit grids a uniform draw puts 3.6 % of the samples ON a pixel crossing of a level
+    whose extents are powers of two; here none is closer to one than 1/32 of a pixel."""
+    x = make_inputs(1, 2, D, 24, 4, [(4, 8)], seed=41, dtype=dtype)
+    x["loc"] = (torch.round(x["loc"] * 64) / 64 + 1.0 / 256).to(dtype).double()
+    return x
+
+
+KINDS = {"ragged": op_inputs, "hot": hot_inputs, "pair": pair_inputs}
+ODD_D = 6            # rows of 12 bytes (16-bit storage) and 24 (fp32): the C contract's ``row_align`` is the element size
+
+
+def op_cases():
+    """(id, inputs) of every input set the placement tests hold grad_loc on."""
+    for dtype in OP_DTYPES:
+        for D in OP_WIDTHS + (ODD_D,):
+            yield f"{str(dtype)[6:]}-D{D}", op_inputs(dtype, D)
+        yield f"{str(dtype)[6:]}-hot", hot_inputs(dtype)
+        yield f"{str(dtype)[6:]}-pair", pair_inputs(dtype)
