@@ -180,6 +180,44 @@ def _aligned(t, nbytes=16):
     return t if t.data_ptr() % nbytes == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
+def _plain(t):
+    """a tensor as the attention entries take it: detached, contiguous, aligned to 16 bytes"""
+    t = t.detach()
+    return _aligned(t if t.is_contiguous() else t.contiguous())
+
+
+# ---- what the attention functions (functions/*attn*_func.py, llama_train_func.py) check and allocate alike
+
+def _attn_supported(q, heads, probe, *more):
+    """a device tensor q [B, L, H D] of bf16 or fp16, outside autocast, that the library's ``probe`` (dtype, D, L, *more) takes"""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dim() == 3) or torch.is_autocast_enabled():
+        return False
+    if q.dtype not in (torch.float16, torch.bfloat16) or heads < 1 or q.shape[2] % heads:
+        return False
+    return bool(getattr(_lib, probe)(_DTYPE_CODE[q.dtype], q.shape[2] // heads, q.shape[1], *more))
+
+
+def _require_qkv(what, q, k, v, heads, head_dim):
+    """q, k, v [B, L, H head_dim] of one half type, shape and device, outside autocast; else a RuntimeError that names ``what``"""
+    _require(all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 for t in (q, k, v)) and
+             q.dtype in (torch.float16, torch.bfloat16), f"{what}: q, k, v must be device tensors [B, L, H {head_dim}] of bf16 or fp16")
+    _require(k.shape == q.shape and v.shape == q.shape and k.dtype == q.dtype and v.dtype == q.dtype and
+             k.device == q.device and v.device == q.device, f"{what}: k and v must have q's shape, type and device")
+    _require(heads >= 1 and q.shape[2] == heads * head_dim, f"{what}: {q.shape[2]} channels are not {heads} heads of {head_dim}")
+    _require(not torch.is_autocast_enabled(), f"{what}: not under autocast")
+
+
+def _tiles(entry, n):
+    """how a kernel family cuts its work, where its paths change: ``entry``(0 .. n - 1)"""
+    return tuple(int(getattr(_lib, entry)(i)) for i in range(n))
+
+
+def _float_workspace(entry, device, *dims):
+    """the fp32 workspace that ``entry``(*dims) sizes in bytes (the caching allocator's, like the outputs: no device
+    allocation in a steady loop)"""
+    return torch.empty(max(getattr(_lib, entry)(*dims) // 4, 4), dtype=torch.float32, device=device)
+
+
 def _stream(device):
     return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
 

@@ -3,7 +3,9 @@
 // mmfs_text_loss.hip takes exp_hw alone): exp by the hardware's exp2, finfo(T).min
 // and the masked-key rule, the fragment helpers of the 16x16x32 matrix products, and on the host side the checks that the
 // LLaMA entries make alike.  The online-softmax tile step of qk_attn_fwd and llama_attn_prefill is NOT here: each kernel
-// keeps its loop (profiles/attn_core.md says what a shared routine measured).
+// keeps its loop (profiles/attn_core.md says what a shared routine measured).  The two TRAINING attentions (mmfs_llama_train.hip,
+// mmfs_clip_attn.hip) do share their three tile walks: mmfs_attn_train.h (attn_train_fwd, attn_train_dq, attn_train_dkdv), on
+// top of this file.
 #pragma once
 #include "msda_host.h"
 #include "msda_mma_common.h"

@@ -16,7 +16,7 @@ HEAD_DIM = 128
 # how the decode kernel cuts the keys: a wave's, a workgroup's (= a split's): where its paths change
 WAVE_KEYS, SPLIT_KEYS = int(_lib.mmfs_llama_attn_decode_keys(0)), int(_lib.mmfs_llama_attn_decode_keys(1))
 # how the prefill kernel cuts its work: the query rows of a wave, of a workgroup, the keys of a tile
-PREFILL_TILES = tuple(int(_lib.mmfs_llama_attn_prefill_tiles(i)) for i in range(3))
+PREFILL_TILES = MSDA._tiles("mmfs_llama_attn_prefill_tiles", 3)
 PREFILL_CAUSAL, PREFILL_VISIT_ALL = 1, 2                # MMFS_LLAMA_PREFILL_*
 
 # kernel launches since import, for tests and tools that ask which route the module took
@@ -37,16 +37,10 @@ def rope_table(head_dim, max_positions, base=10000, device=None):
 
 def llama_attn_supported(q, heads, cap):
     """The kernels apply: a device tensor q [B, Lq, H 128] of bf16 or fp16, 1 <= Lq <= cap, outside autocast."""
-    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dim() == 3) or torch.is_autocast_enabled():
-        return False
-    if q.dtype not in _CODE or heads < 1 or q.shape[2] % heads:
-        return False
-    return bool(_lib.mmfs_llama_attn_supported(_CODE[q.dtype], q.shape[2] // heads, q.shape[1], cap))
+    return MSDA._attn_supported(q, heads, "mmfs_llama_attn_supported", cap)
 
 
-def _require(cond, what):
-    if not cond:
-        raise RuntimeError(what)
+_require, _plain = MSDA._require, MSDA._plain
 
 
 def _check_cache(q, keys, values, length, src_row, what):
@@ -61,11 +55,6 @@ def _check_cache(q, keys, values, length, src_row, what):
     _require(length.dtype == torch.int32 and length.device == dev and length.numel() == 1, f"{what}: length must be one int32 on q's device")
     _require(src_row.dtype == torch.int32 and src_row.device == dev and src_row.is_contiguous()
              and tuple(src_row.shape) == (keys.shape[0], keys.shape[2]), f"{what}: src_row must be contiguous int32 [B, cap] on q's device")
-
-
-def _plain(t):
-    t = t.detach()
-    return MSDA._aligned(t if t.is_contiguous() else t.contiguous())
 
 
 def _bias_args(bias, dev, dt):

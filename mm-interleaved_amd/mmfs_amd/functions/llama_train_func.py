@@ -14,12 +14,11 @@ from torch.autograd.function import once_differentiable
 
 import MultiScaleDeformableAttention as MSDA
 
-_lib = MSDA._lib
 _CODE = MSDA._DTYPE_CODE
 HEAD_DIM = 128
 # how the kernels cut their work, where their paths change: the query rows of a workgroup (forward, dq), the keys of a
 # forward tile, the keys of a dkdv workgroup, the queries of a dkdv tile, the query rows of a wave
-TRAIN_TILES = tuple(int(_lib.mmfs_llama_attn_train_tiles(i)) for i in range(5))
+TRAIN_TILES = MSDA._tiles("mmfs_llama_attn_train_tiles", 5)
 
 # kernel launches since import, for tests and tools that ask which route the module took
 launches = {"rope": 0, "forward": 0, "backward": 0}
@@ -27,16 +26,7 @@ launches = {"rope": 0, "forward": 0, "backward": 0}
 
 def llama_attn_train_supported(q, heads):
     """The kernels apply: a device tensor q [B, L, H 128] of bf16 or fp16, L >= 1, outside autocast."""
-    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dim() == 3) or torch.is_autocast_enabled():
-        return False
-    if q.dtype not in (torch.float16, torch.bfloat16) or heads < 1 or q.shape[2] % heads:
-        return False
-    return bool(_lib.mmfs_llama_attn_train_supported(_CODE[q.dtype], q.shape[2] // heads, q.shape[1]))
-
-
-def _plain(t):
-    t = t.detach()
-    return MSDA._aligned(t if t.is_contiguous() else t.contiguous())
+    return MSDA._attn_supported(q, heads, "mmfs_llama_attn_train_supported")
 
 
 def _positions(position_ids, B, L, dev):
@@ -47,7 +37,7 @@ def _positions(position_ids, B, L, dev):
 
 
 def train_rope(q, k, pos, cos, sin, heads):
-    """-> (q_rot, k_rot); the arguments as ``_positions`` and ``_plain`` leave them"""
+    """-> (q_rot, k_rot); the arguments as ``_positions`` and ``MSDA._plain`` leave them"""
     B, L, C = q.shape
     q_rot, k_rot = torch.empty_like(q), torch.empty_like(k)
     MSDA._call("llama_train_rope", "mmfs_llama_attn_train_rope", q.device, _CODE[q.dtype], q.data_ptr(), k.data_ptr(),
@@ -73,8 +63,7 @@ def train_backward(q_rot, k_rot, v, out, grad, lse, pos, cos, sin, heads):
     B, L, C = q_rot.shape
     dev = q_rot.device
     dq, dk, dv = torch.empty_like(q_rot), torch.empty_like(q_rot), torch.empty_like(q_rot)
-    # delta (the caching allocator's, like the outputs: no device allocation in a steady loop)
-    ws = torch.empty(max(_lib.mmfs_llama_attn_train_workspace_bytes(B, heads, L) // 4, 4), dtype=torch.float32, device=dev)
+    ws = MSDA._float_workspace("mmfs_llama_attn_train_workspace_bytes", dev, B, heads, L)       # delta
     MSDA._call("llama_train_bwd", "mmfs_llama_attn_train_backward", dev, _CODE[q_rot.dtype], q_rot.data_ptr(), k_rot.data_ptr(),
                v.data_ptr(), out.data_ptr(), grad.data_ptr(), lse.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                cos.shape[0], dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, L, heads, C // heads)
@@ -90,7 +79,7 @@ class LlamaAttnTrainFunction(Function):
     @staticmethod
     def forward(ctx, q, k, v, position_ids, cos, sin, heads):
         B, L, _ = q.shape
-        q, k, v = _plain(q), _plain(k), _plain(v)
+        q, k, v = MSDA._plain(q), MSDA._plain(k), MSDA._plain(v)
         pos = _positions(position_ids, B, L, q.device)
         q_rot, k_rot = train_rope(q, k, pos, cos, sin, heads)
         out, lse = train_forward(q_rot, k_rot, v, heads)
@@ -107,25 +96,15 @@ class LlamaAttnTrainFunction(Function):
         return dq, dk, dv, None, None, None, None
 
 
-def _require(cond, what):
-    if not cond:
-        raise RuntimeError(what)
-
-
 def llama_attn_train(q, k, v, position_ids, cos, sin, heads):
     """q, k, v [B, L, H 128] device tensors of bf16 or fp16 as the Linear layers return them, position_ids [B, L] (or
     [1, L]) integers, (cos, sin) of ``rope_table`` on the device -> context [B, L, H 128]:
     softmax over the keys t <= j of rope(q)[b, j] . rope(k)[b, t] / sqrt(128), times v.  Differentiable in q, k and v."""
-    _require(all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 for t in (q, k, v)) and
-             q.dtype in (torch.float16, torch.bfloat16), "llama_attn_train: q, k, v must be device tensors [B, L, H 128] of bf16 or fp16")
-    _require(k.shape == q.shape and v.shape == q.shape and k.dtype == q.dtype and v.dtype == q.dtype and
-             k.device == q.device and v.device == q.device, "llama_attn_train: k and v must have q's shape, type and device")
-    _require(heads >= 1 and q.shape[2] == heads * HEAD_DIM, f"llama_attn_train: {q.shape[2]} channels are not {heads} heads of 128")
+    MSDA._require_qkv("llama_attn_train", q, k, v, heads, HEAD_DIM)
     B, L, _ = q.shape
     for name, t in (("cos", cos), ("sin", sin)):
-        _require(t.dtype == torch.float32 and t.device == q.device and t.is_contiguous() and t.dim() == 2 and
+        MSDA._require(t.dtype == torch.float32 and t.device == q.device and t.is_contiguous() and t.dim() == 2 and
                  t.shape[1] == HEAD_DIM // 2 and t.shape == cos.shape and t.data_ptr() % 16 == 0,
                  f"llama_attn_train: {name} must be contiguous fp32 [max_pos, 64] on q's device (rope_table)")
-    _require(position_ids.numel() in (L, B * L), "llama_attn_train: position_ids must be [B, L] (or [1, L])")
-    _require(not torch.is_autocast_enabled(), "llama_attn_train: not under autocast")
+    MSDA._require(position_ids.numel() in (L, B * L), "llama_attn_train: position_ids must be [B, L] (or [1, L])")
     return LlamaAttnTrainFunction.apply(q, k, v, position_ids, cos, sin, heads)
